@@ -8,6 +8,14 @@ of python/fedml/ml/aggregator/agg_operator.py:35-44), value = algorithmic bytes 
 B = K*P*4 (reads) + P*4 (write) = 64.5 GB.
 
   python bench.py [--gpus N --steps K --warmup W] [--config metric|resnet18|vit_bf16|hier|gossip]
+                  [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, the
+roofline of the timed steps themselves).  ``--full`` adds everything measured or checked beside
+that figure: the read-ceiling probe, the clock samples, the soak, the cold calls, the parity check
+against the oracle and the CPU baseline (``parity`` and ``cpu_baseline`` are null without it).
+``--dump-outputs DIR`` writes what the last timed step computed as DIR/<name>.npy (dump_outputs);
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 N > 1 (one rank per GPU, RCCL over xGMI): ``python bench.py --gpus N`` starts its N ranks itself
 (torch.distributed.run as a child process, before anything touches the GPU); under an outer
@@ -67,6 +75,15 @@ def parse():
     p.add_argument("--warmup", type=int, default=None,
                    help="untimed warmup steps (default: 3, and on one GPU as many more as make ~1 s of the "
                         "workload's own steps -- short steps otherwise run on the clock ramp, DESIGN A.2 3b)")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure: the read-ceiling probe, the clock sampler, "
+                        "the soak, the cold calls, the parity check against the oracle, the CPU baseline and the "
+                        "configs' own extra measurements (their fields are null or absent without it)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed (the arrays its caller "
+                        "receives) as DIR/<name>.npy, float32 (float64 for int64 / float64 results), at most 64 MB "
+                        "in all: an array past its share is written as a fixed sample of its 1024-element tiles "
+                        "(dump_outputs)")
     p.add_argument("--config", default="metric",
                    choices=["metric", "fragmented", "resnet18", "vit_bf16", "hier", "gossip", "host", "secagg", "fedopt",
                             "dropin_cpu", "median",
@@ -130,6 +147,8 @@ def parse():
                         "FedMLAggOperator.agg.  Default: tiled, except gossip (arena: its "
                         "row-sequential sliding window measured 5.12 ms client-major vs 5.52 ms tiled)")
     a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps: at least one timed step")
     if a.layout is None:
         a.layout = "arena" if a.config == "gossip" else "tiled"
     return a
@@ -418,6 +437,36 @@ def tiled_pick(buf, tiles, P):
     return torch.cat(cols, dim=1)
 
 
+DUMP_BUDGET = 48 << 20  # bytes of array data per --dump-outputs run (the option's limit is 64 MB)
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET, E=1024, seed=2024):
+    """--dump-outputs: write ``arrays`` (name -> tensor, on any device) as ``path``/<name>.npy, float32
+    (bf16 / fp16 / fp32 results) or float64 (int64 / float64 results, exact below 2^53).  When everything
+    together would exceed ``budget`` bytes, every array gets an equal share of it, and an array past
+    its share is written as a sample: whole E-element tiles of its flattened form, chosen by
+    sample_tiles (a fixed seed and the array's size only, so two builds sample the same elements),
+    in ascending order.  Returns {file name: elements written}."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+
+    def wide(t):
+        return torch.float64 if t.dtype in (torch.int64, torch.float64) else torch.float32
+    size = {k: v.numel() * (8 if wide(v) == torch.float64 else 4) for k, v in arrays.items()}
+    share = budget if sum(size.values()) <= budget else budget // max(1, len(arrays))
+    done = {}
+    for k, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        if size[k] > share:
+            per = 8 if wide(t) == torch.float64 else 4
+            flat = flat_pick(flat, sample_tiles(n, max(1, share // (per * E)), seed, E), n, E)
+        name = "".join(c if c.isalnum() or c in "._-" else "_" for c in str(k)) + ".npy"
+        np.save(os.path.join(path, name), flat.cpu().to(wide(t)).numpy())
+        done[name] = int(flat.numel())
+    return done
+
+
 def load_layout(name):
     with open(os.path.join(ROOT, "tests", "golden", "layouts.json")) as f:
         return json.load(f)[name]
@@ -683,7 +732,7 @@ def wl_metric(args, eng, rank, world, timer):
 
     suffix = {"arena": "", "tiled": "_tiled", "tensors": "_tensors"}[args.layout]
     return dict(loop_timing=True, name=f"fedavg_flat_K{K}_P{P}_fp32" + suffix,
-                dtype="fp32", step=step, parity=parity,
+                dtype="fp32", step=step, parity=parity, outputs=lambda: {"global_model": res.get("g")},
                 bytes_total=K * P * 4 + P * 4, launch_bytes=(len(mine) * P * 4 + P * 4) / launches,
                 clients=K, params=P, cpu_K=K,
                 probe=(buf, buf.shape[1], f"this workload's tiled arena group ({buf.shape[1]} consecutive 4-KiB rows "
@@ -797,7 +846,7 @@ def wl_layout(args, eng, rank, world, timer):
     tag = ("resnet18gn" if resnet else "vitb16_bf16") + {"arena": "", "tiled": "_tiled", "tensors": "_tensors",
                                                          "adopted": "_adopted_agg"}[args.layout]
     return dict(loop_timing=True, name=f"fedavg_{tag}_K{K}_P{P}", dtype="fp32" if resnet else "bf16", step=step, parity=parity,
-                bytes_total=K * in_b + out_b, launch_bytes=None, clients=K, params=P, cpu_K=None,
+                outputs=lambda: dict(res.get("out") or {}), bytes_total=K * in_b + out_b, launch_bytes=None, clients=K, params=P, cpu_K=None,
                 step_bytes=len(mine) * in_b + out_b if world > 1 else None)
 
 
@@ -867,6 +916,7 @@ def wl_dropin_cpu(args, eng, rank, world, timer):
                            "(agg_operator.py:35-44)")
 
     return dict(name=f"dropin_agg_cpu_resnet18gn_K{K}_P{P}", dtype="fp32", step=step, parity=parity, cpu=cpu,
+                outputs=lambda: dict(res["out"]),
                 bytes_total=K * in_b + out_b, launch_bytes=None, clients=K, params=P, cpu_K=K,
                 data="synthetic CPU state_dicts (ResNet-18-GN layout), host-resident: the step includes H2D and D2H",
                 roofline_note="kernel time = the whole agg() call incl. PCIe transfers (host-resident inputs)")
@@ -965,7 +1015,7 @@ def wl_arrival(args, eng, rank, world, timer):
                           f"K={K} CPU state_dicts, started once all have arrived; best of runs per thread count"}
 
     return dict(name=f"arrival_fedavg_resnet18gn_K{K}_P{P}", dtype="fp32", step=step, parity=parity, cpu=cpu,
-                latency=True, extra=res, clients=K, params=P, cpu_K=K, bytes_total=None, launch_bytes=None,
+                outputs=lambda: dict(res["host"]), latency=True, extra=res, clients=K, params=P, cpu_K=K, bytes_total=None, launch_bytes=None,
                 data=f"synthetic CPU state_dicts (ResNet-18-GN layout) arriving {args.arrival_gap_ms} ms apart; "
                      "ingested to HBM on arrival; result D2H to pinned host memory",
                 metric_name=f"last-arrival -> host-resident global model latency, cross-silo FedAvg round, "
@@ -1084,7 +1134,7 @@ def wl_lr(args, eng, rank, world, timer):
 
     P = sum(int(np.prod(s)) for _, s, _ in layout)
     return dict(name=f"fedavg_lr_mnist_K{K}_P{P}_{mode}", dtype="fp32", step=step, parity=parity_and_sweep, cpu=cpu,
-                extra_line=extra,
+                extra_line=extra, outputs=lambda: dict(res["out"]),
                 latency=True, stat="median", clients=K, params=P, cpu_K=K, bytes_total=None, launch_bytes=None,
                 data=f"synthetic LR-MNIST updates (784x10 + 10 fp32), {'CPU' if mode == 'host' else 'device'} "
                      f"state_dicts{' adopted into arena rows' if mode == 'adopted' else ''}",
@@ -1145,6 +1195,7 @@ def wl_fragmented(args, eng, rank, world, timer):
         return f"{'bit-exact' if bad == 0 else f'{bad} MISMATCHES'} vs oracle on a strided sample of 16 keys"
 
     return dict(loop_timing=True, name=f"fedavg_fragmented{len(layout)}_K{K}_P{P}_fp32", dtype="fp32", step=step, parity=parity,
+                outputs=lambda: dict(res["out"]),
                 bytes_total=K * P * 4 + P * 4, launch_bytes=None, clients=K, params=P, cpu_K=None,
                 roofline_note="kernel time = the whole aggregate() call (host pointer tables + launch + kernel)")
 
@@ -1239,7 +1290,7 @@ def wl_hier(args, eng, rank, world, timer):
                 f"elements" + (f" of {collective_note(args, world)}" if world > 1 else ""))
 
     return dict(loop_timing=True, name=f"hier_fedavg_G{G}x{M}_P{P}_fp32" + ("_tiled" if tiled else ""), dtype="fp32", step=step, parity=parity,
-                bytes_total=G * M * P * 4 + P * 4, launch_bytes=(len(clients) * P * 4 + P * 4) / launches,
+                outputs=lambda: {"global_model": res.get("g")}, bytes_total=G * M * P * 4 + P * 4, launch_bytes=(len(clients) * P * 4 + P * 4) / launches,
                 clients=G * M, params=P, cpu_K=None)
 
 
@@ -1326,6 +1377,8 @@ def wl_gossip(args, eng, rank, world, timer):
                 f"sampled elements over all {n} nodes" + (f" ({world} ranks, halo exchange)" if world > 1 else ""))
 
     return dict(name=f"gossip_ring_n{n}_P{P}_fp32" + ("_tiled" if tiled else ""), dtype="fp32", step=step,
+                outputs=lambda: ({"mixed_arena": obuf} if tiled else
+                                 {f"node_{i:04d}": o for i, o in zip(nodes, res["outs"])}),
                 parity=parity, bytes_total=2 * n * P * 4, launch_bytes=2 * rows * P * 4, clients=n, params=P,
                 cpu_K=None, step_bytes=2 * rows * P * 4 if world > 1 else None,
                 roofline_note="compulsory bytes 2*n*P*4 (each model read once, each mixed model written once); "
@@ -1372,7 +1425,7 @@ def wl_host(args, eng, rank, world, timer):
     del base
     arena = ClientArena(ArenaLayout([("w", (P,), torch.float32)]), capacity=K)
     result = torch.empty(P, pin_memory=True)
-    pcie = pcie_probe()
+    pcie = pcie_probe() if args.full else None  # a measurement beside the headline figure
 
     def step():
         for i in range(K):
@@ -1394,14 +1447,17 @@ def wl_host(args, eng, rank, world, timer):
         bad = count_bad(got, exp)
         return f"{'bit-exact' if bad == 0 else f'{bad} MISMATCHES'} vs oracle on {exp.numel()} sampled elements"
 
-    pcie_floor_ms = ((K * P * 4) / (pcie["pinned_h2d_GBs"] * 1e9) + P * 4 / (pcie["pinned_d2h_GBs"] * 1e9)) * 1e3
+    pcie_line = {}
+    if pcie is not None:
+        floor_ms = ((K * P * 4) / (pcie["pinned_h2d_GBs"] * 1e9) + P * 4 / (pcie["pinned_d2h_GBs"] * 1e9)) * 1e3
+        pcie_line["pcie"] = dict(pcie, floor_ms_per_step=round(floor_ms, 2),
+                                 note="K*P*4 B H2D + P*4 B D2H at the pinned copy rates")
     return dict(name=f"fedavg_host_ingest_{'pinned' if args.pinned else 'pageable'}_K{K}_P{P}_fp32", dtype="fp32",
                 step=step, parity=parity, bytes_total=K * P * 4 + P * 4, launch_bytes=K * P * 4 + P * 4, clients=K,
-                params=P, cpu_K=None,
+                params=P, cpu_K=None, outputs=lambda: {"global_model": result},
                 data=f"synthetic N(0,1) client updates in {'pinned' if args.pinned else 'pageable'} HOST memory "
                      "(client i = window i of one random vector), n_i ~ U{50..600} (seed 7)",
-                extra_line={"pcie": dict(pcie, floor_ms_per_step=round(pcie_floor_ms, 2),
-                                         note="K*P*4 B H2D + P*4 B D2H at the pinned copy rates")},
+                extra_line=pcie_line,
                 roofline_note="value includes the H2D of every update (pageable: packed through pinned staging), "
                               "the aggregation and the D2H of the result; `pcie` holds this box's pinned copy rates")
 
@@ -1480,7 +1536,7 @@ def wl_fedopt(args, eng, rank, world, timer):
                            f"+ torch.optim.SGD(momentum={mom}) step")
 
     return dict(name=f"fedopt_sgd_K{K}_P{P}_fp32" + ("_tiled" if tiled else ""), dtype="fp32", step=step, parity=parity, cpu=cpu,
-                bytes_total=(K + 4) * P * 4, launch_bytes=(K + 4) * P * 4, clients=K, params=P, cpu_K=K)
+                outputs=lambda: {"param": param, "momentum": mbuf}, bytes_total=(K + 4) * P * 4, launch_bytes=(K + 4) * P * 4, clients=K, params=P, cpu_K=K)
 
 
 def wl_secagg(args, eng, rank, world, timer):
@@ -1562,6 +1618,7 @@ def wl_secagg(args, eng, rank, world, timer):
 
     recon = K * P * 8 + P * 8 + P * 4
     return dict(name=f"lightsecagg_reconstruct_N{K}_P{P}_int64" + ("_tiled" if tiled else ""), dtype="int64", step=step, parity=parity,
+                outputs=lambda: {"model": state["real"], "mask": state["mask"]},
                 data="synthetic masked finite models uniform in Z_p (p = 2^15-19, q = 10 bits), resident in HBM",
                 bytes_total=recon + U * m * 8 + P * 8, launch_bytes=recon, clients=K, params=P, cpu_K=K, cpu=cpu,
                 roofline_note="dominant kernel = fa_finite_sum (K masked models + mask in, fp32 out); value also "
@@ -1631,6 +1688,7 @@ def wl_samask(args, eng, rank, world, timer):
 
     return dict(name=f"secagg_mask_expand_N{K}_dropped{dropped}_P{P}_int64", dtype="u32 (MT19937) -> int64", step=step,
                 parity=parity, cpu=cpu, latency=True, stat="median", clients=K, params=P, cpu_K=K, bytes_total=None,
+                outputs=lambda: {"mask_sum": out},
                 launch_bytes=None, metric_name=f"SecAgg mask re-expansion latency, {len(seeds)} streams x {P} draws",
                 data=f"{len(seeds)} MT19937 streams (seeds from RandomState(5)), p = 2^31 - 1")
 
@@ -1706,7 +1764,7 @@ def wl_median(args, eng, rank, world, timer):
     return dict(loop_timing=True, name=f"coord_median_K{K}_P{P}_{args.dtype}" + ("_tiled" if tiled else ""), dtype=args.dtype,
                 probe=(buf, buf.shape[1], f"this workload's tiled arena group ({buf.shape[1]} consecutive 4-KiB rows "
                        "per workgroup)") if tiled else None,
-                step=step, parity=parity,
+                step=step, parity=parity, outputs=lambda: {"median": out},
                 bytes_total=(K * P + P) * es, launch_bytes=(K * P + P) * es, clients=K, params=P, cpu_K=K, cpu=cpu,
                 data="synthetic N(0,1) client weight vectors, resident in HBM (" +
                      ("tile-interleaved ClientArena rows)" if tiled else "rows 256-byte aligned)"))
@@ -1757,7 +1815,7 @@ def wl_krum(args, eng, rank, world, timer):
                                    "when kappa_max <= 16; direct: the VALU difference kernel")
         return p
     return dict(loop_timing=True, name=f"krum_pairdist_K{K}_P{P}_fp32", dtype="fp32", step=step, parity=parity_and_form,
-                extra_line=extra,
+                extra_line=extra, outputs=lambda: {"pairwise_sqdist": state["D"]},
                 bytes_total=K * P * 4, launch_bytes=K * P * 4, clients=K, params=P, cpu_K=K, cpu=cpu,
                 data="synthetic N(0,1) client weight vectors, resident in HBM (rows 256-byte aligned)",
                 mfma_flops_per_launch=K * (K + 1) * P, mfma_bound=K > 32,
@@ -2110,7 +2168,10 @@ def main():
     timer.loop = bool(wl.get("loop_timing")) and world == 1 and not args.loopback
     # amdsmi's init takes ~0.1 s: before the warmup, so that it never leaves the GPU idle (and its
     # clocks and power down) right before the timed steps (r06af)
-    clk = None if CPU_REHEARSAL or args.no_clock or rank != 0 or wl.get("latency") else ClockSampler(local)
+    # --full only, like everything below that the headline figure does not need (the probe, the soak,
+    # the cold calls, the parity check, the CPU baseline)
+    clk = None if not args.full or CPU_REHEARSAL or args.no_clock or rank != 0 or wl.get("latency") \
+        else ClockSampler(local)
     auto_warmup = args.warmup is None
     if auto_warmup:
         args.warmup = 3
@@ -2133,7 +2194,7 @@ def main():
         sync()
         args.warmup += 1 + extra
     ceiling = None
-    if world == 1 and not CPU_REHEARSAL and not args.no_read_probe and not wl.get("latency"):
+    if args.full and world == 1 and not CPU_REHEARSAL and not args.no_read_probe and not wl.get("latency"):
         stage("read probe")
         with ClockSampler.maybe(clk) as cs:
             ceiling = read_ceiling(eng, wl)
@@ -2169,8 +2230,12 @@ def main():
     if clk_edges is not None:  # (after the clock stops: a sample takes ~1-5 ms, r06aj)
         clk_edges.append(clk.sample_now())
     timer.stop()
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before anything steps again: the last TIMED step's results
+        stage("dump outputs")
+        dumped = dump_outputs(args.dump_outputs, wl["outputs"]())
     sustained = None
-    if args.soak_seconds > 0 and world == 1 and not wl.get("latency") and wl.get("bytes_total"):
+    if args.full and args.soak_seconds > 0 and world == 1 and not wl.get("latency") and wl.get("bytes_total"):
         stage("soak")
         n_soak = 0
         sync()
@@ -2186,7 +2251,7 @@ def main():
                      "ms_per_step": round(dt_s / n_soak * 1e3, 4),
                      "note": "the same step repeated after the timed region (not part of `value`)"}
     cold = None
-    if args.cold_reps > 0 and world == 1 and not CPU_REHEARSAL:
+    if args.full and args.cold_reps > 0 and world == 1 and not CPU_REHEARSAL:
         stage("cold calls")
         cold = cold_calls(wl, args.cold_reps, args.cold_idle)
     stage("parity check")
@@ -2204,10 +2269,10 @@ def main():
     elif launch_bytes is None and kernel_ms and wl.get("bytes_total"):  # layout configs: the whole call per step
         launch_bytes = wl["bytes_total"] / world
     achieved = launch_bytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms and launch_bytes else None
-    parity = wl["parity"]()
+    parity = wl["parity"]() if args.full else None
     cpu = None
     stage("cpu baseline")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and wl.get("cpu_K"):
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and wl.get("cpu_K"):
         cpu = wl["cpu"](args.cpu_seconds) if wl.get("cpu") else cpu_baseline(wl["cpu_K"], args.cpu_seconds)
         cpu.setdefault("cpu_model", cpu_model())
         cpu.setdefault("os_cpu_count", os.cpu_count())
@@ -2244,7 +2309,10 @@ def main():
             "roofline": roofline_block(wl, world, value, unit, achieved, kernel_ms, launch_bytes),
             "cpu_baseline": cpu,
             "parity": parity,
+            "full": args.full,
         }
+        if dumped is not None:
+            line["outputs"] = {"dir": args.dump_outputs, "arrays": len(dumped), "elements": sum(dumped.values())}
         if wl.get("roofline_note"):
             line["roofline"]["note"] = wl["roofline_note"]
         if ceiling is not None:

@@ -32,7 +32,7 @@ def run(extra, gpus=8, timeout=600):
                PYTHONPATH=os.path.join(ROOT, "tests") + os.pathsep + os.environ.get("PYTHONPATH", ""),
                OMP_NUM_THREADS="1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1",
-           "--soak-seconds", "0", "--no-cpu-baseline"] + extra
+           "--full", "--soak-seconds", "0", "--no-cpu-baseline"] + extra  # --full: the line's parity
     t0 = time.perf_counter()
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
     wall = time.perf_counter() - t0
