@@ -505,6 +505,30 @@ class ClientArena:
                 outs[dt] = o
         return self.layout.carve(outs)
 
+    def trimmed_mean(self, trim: int, clients: Optional[Sequence[int]] = None,
+                     out: Optional[Dict[torch.dtype, torch.Tensor]] = None) -> "OrderedDict[str, torch.Tensor]":
+        """Coordinate-wise trimmed mean (Yin et al. 2018; include/fedagg_robust.h) over the given
+        client rows (default: all) with ``trim`` values dropped at each end of every column, one launch
+        per dtype group: tiled arenas through fa_coord_trimmed_mean_tiled, client-major arenas over the
+        row views.  Float groups only.  Returns per-key views."""
+        clients = list(range(self.capacity)) if clients is None else list(clients)
+        if not clients:
+            raise ValueError("trimmed_mean: no client rows")
+        if any(dt not in (torch.float32, torch.bfloat16, torch.float16, torch.float64) for dt in self.bufs):
+            raise TypeError("trimmed_mean: the arena holds a non-float dtype group")
+        self._wait_ingest()
+        outs: Dict[torch.dtype, torch.Tensor] = {}
+        for dt, buf in self.bufs.items():
+            o = out[dt] if out is not None else None
+            n = self.layout.group_numel[dt]
+            if self.tiled:
+                outs[dt] = self.engine.coord_trimmed_mean_tiled(buf, clients, trim, n=n, out=o)
+            else:
+                o = o if o is not None else torch.empty(n, dtype=dt, device=buf.device)
+                self.engine.coord_trimmed_mean([[buf[i][:n] for i in clients]], trim, outs=[o])
+                outs[dt] = o
+        return self.layout.carve(outs)
+
     def _pair_groups(self) -> Optional[torch.dtype]:
         """The float dtype when the arena holds exactly one float group and one int64 group."""
         dts = list(self.bufs)

@@ -1,7 +1,9 @@
 """FedMLDefender singleton (reference: python/fedml/core/security/fedml_defender.py:40-196) for the
-robust aggregators of this engine: krum / multikrum, trimmed_mean and wise_median.  Same dispatch
+robust aggregators of this engine: krum / multikrum, trimmed_mean, wise_median and
+coordinate_trimmed_mean (the per-coordinate trimmed mean of Yin et al. 2018, which the reference
+lacks: its trimmed_mean trims whole clients and keeps that meaning here).  Same dispatch
 (which defenses act before / on / after aggregation) and the same entry points; the per-element work
-runs in the HIP kernels (fedml_amd/csrc/robust.hip).  Other defense types of the reference are
+runs in the HIP kernels (fedml_amd/csrc/robust.hip, trimmed.hip).  Other defense types of the reference are
 outside the aggregation path and raise NotImplementedError when configured.
 """
 from __future__ import annotations
@@ -10,7 +12,9 @@ import logging
 from collections import OrderedDict
 from typing import Any, Callable, List, Tuple
 
-from .constants import DEFENSE_KRUM, DEFENSE_MULTIKRUM, DEFENSE_TRIMMED_MEAN, DEFENSE_WISE_MEDIAN
+from .constants import (DEFENSE_COORD_TRIMMED_MEAN, DEFENSE_KRUM, DEFENSE_MULTIKRUM, DEFENSE_TRIMMED_MEAN,
+                        DEFENSE_WISE_MEDIAN)
+from .defense.coordinate_trimmed_mean_defense import CoordinateTrimmedMeanDefense
 from .defense.coordinate_wise_median_defense import CoordinateWiseMedianDefense
 from .defense.coordinate_wise_trimmed_mean_defense import CoordinateWiseTrimmedMeanDefense
 from .defense.krum_defense import KrumDefense
@@ -42,10 +46,12 @@ class FedMLDefender:
                 self.defender = CoordinateWiseMedianDefense(args)
             elif self.defense_type == DEFENSE_TRIMMED_MEAN:
                 self.defender = CoordinateWiseTrimmedMeanDefense(args)
+            elif self.defense_type == DEFENSE_COORD_TRIMMED_MEAN:
+                self.defender = CoordinateTrimmedMeanDefense(args)
             else:
                 raise NotImplementedError(
                     f"defense_type {self.defense_type!r} is not served by the MI355X engine "
-                    f"(supported: krum, multikrum, trimmed_mean, wise_median)")
+                    f"(supported: krum, multikrum, trimmed_mean, wise_median, coordinate_trimmed_mean)")
         else:
             self.is_enabled = False
             self.defense_type = None
@@ -55,7 +61,8 @@ class FedMLDefender:
         return self.is_enabled
 
     def is_defense_on_aggregation(self):
-        return self.is_defense_enabled() and self.defense_type in [DEFENSE_WISE_MEDIAN]
+        return self.is_defense_enabled() and self.defense_type in [DEFENSE_WISE_MEDIAN,
+                                                                               DEFENSE_COORD_TRIMMED_MEAN]
 
     def is_defense_before_aggregation(self):
         return self.is_defense_enabled() and self.defense_type in [DEFENSE_KRUM, DEFENSE_MULTIKRUM,

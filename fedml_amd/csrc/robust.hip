@@ -25,6 +25,7 @@
 
 #include "fa_internal.h"
 #include "fedagg_robust.h"
+#include "median_common.h"
 #include "median_nets.h"
 
 using namespace fa_detail;
@@ -32,107 +33,7 @@ using namespace fa_detail;
 namespace {
 
 
-// Raw element loads in the global address space (global_load_*: vmcnt only).  Generic (flat)
-// loads also count in lgkmcnt, so every s_waitcnt for the next scalar pointer load drained them and
-// the per-client loads of a column ran one HBM round trip at a time.
-template <typename T>
-__device__ __forceinline__ T gld(const void* p, int64_t e) {
-  return ((const __attribute__((address_space(1))) T*)p)[e];
-}
-
-// non-temporal: each client element is read once (K = 16 / 32 medians 6% / 3% faster)
-template <typename T>
-__device__ __forceinline__ T gld_nt(const void* p, int64_t e) {
-  return __builtin_nontemporal_load((const __attribute__((address_space(1))) T*)p + e);
-}
-
-// uniform base + 32-bit byte offset (zero-extended): selects the saddr form of global_load
-template <typename T>
-__device__ __forceinline__ T gld_nt_off(const void* p, unsigned off) {
-  return __builtin_nontemporal_load((const __attribute__((address_space(1))) T*)((const char*)p + off));
-}
-
-template <int DT> struct MedT;
-template <> struct MedT<FA_DTYPE_F32> {
-  using S = unsigned;
-  static constexpr int kBytes = 4;
-  __device__ static float load(const void* p, int64_t e) { return gld_nt<float>(p, e); }
-  __device__ static float load_off(const void* p, unsigned off) { return gld_nt_off<float>(p, off); }
-  __device__ static void store(void* p, int64_t e, float v) { ((float*)p)[e] = v; }
-  __device__ static void store_bits(void* p, int64_t e, const void* src) { ((unsigned*)p)[e] = ((const unsigned*)src)[e]; }
-  __device__ static void store_bits_off(void* p, int64_t e, const void* src, unsigned off) {
-    ((unsigned*)p)[e] = gld_nt_off<unsigned>(src, off);
-  }
-};
-template <> struct MedT<FA_DTYPE_BF16> {
-  static constexpr int kBytes = 2;
-  __device__ static float load(const void* p, int64_t e) {
-    return __uint_as_float((unsigned)gld_nt<unsigned short>(p, e) << 16);
-  }
-  __device__ static float load_off(const void* p, unsigned off) {
-    return __uint_as_float((unsigned)gld_nt_off<unsigned short>(p, off) << 16);
-  }
-  __device__ static void store(void* p, int64_t e, float v) {
-    ((unsigned short*)p)[e] = (unsigned short)(__float_as_uint(v) >> 16);  // exact: v came from bf16
-  }
-  __device__ static void store_bits(void* p, int64_t e, const void* src) {
-    ((unsigned short*)p)[e] = ((const unsigned short*)src)[e];
-  }
-  __device__ static void store_bits_off(void* p, int64_t e, const void* src, unsigned off) {
-    ((unsigned short*)p)[e] = gld_nt_off<unsigned short>(src, off);
-  }
-};
-template <> struct MedT<FA_DTYPE_F16> {
-  static constexpr int kBytes = 2;
-  __device__ static float load(const void* p, int64_t e) {
-    return (float)__builtin_bit_cast(_Float16, gld_nt<unsigned short>(p, e));
-  }
-  __device__ static float load_off(const void* p, unsigned off) {
-    return (float)__builtin_bit_cast(_Float16, gld_nt_off<unsigned short>(p, off));
-  }
-  __device__ static void store(void* p, int64_t e, float v) {
-    ((unsigned short*)p)[e] = __builtin_bit_cast(unsigned short, (_Float16)v);  // exact: v came from f16
-  }
-  __device__ static void store_bits(void* p, int64_t e, const void* src) {
-    ((unsigned short*)p)[e] = ((const unsigned short*)src)[e];
-  }
-  __device__ static void store_bits_off(void* p, int64_t e, const void* src, unsigned off) {
-    ((unsigned short*)p)[e] = gld_nt_off<unsigned short>(src, off);
-  }
-};
-
-// order-preserving key of a float (unsigned order == numeric order for non-NaN values; -0.0 sorts
-// just below +0.0, which the zero rescan below accounts for)
-__device__ __forceinline__ unsigned fkey(float x) {
-  const unsigned u = __float_as_uint(x);
-  return u ^ ((unsigned)((int)u >> 31) | 0x80000000u);
-}
-constexpr unsigned kPosZeroKey = 0x80000000u, kNegZeroKey = 0x7FFFFFFFu;
-__device__ __forceinline__ float fkey_inv(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-
-struct MSeg {
-  int64_t numel;
-  int64_t tile_start;
-  void* out;
-  int64_t tstride;  // 0: flat client segments; > 0: tile-interleaved inputs, bytes between a client's tiles
-  int32_t ptr_base;
-  int32_t pad;
-};
-static_assert(sizeof(MSeg) == 40, "MSeg layout");
-
-// Byte offset of a workgroup's first column e0 from a client's segment start: flat segments e0 * SZ;
-// tiled inputs (tstride > 0, FA_TILE_BYTES tiles of E elements; fedml_amd/arena.py tiled=True)
-// (e0 / E) * tstride + (e0 % E) * SZ.  A workgroup's columns never straddle a tile (its column count
-// divides E), so a client's element is `uniform base (SGPRs: pointer + this offset) + the lane's
-// 32-bit byte offset` in both layouts -- every load keeps global_load's saddr form, for any segment size.
-template <int SZ>
-__device__ __forceinline__ int64_t col_base(int64_t e0, int64_t tstride) {
-  constexpr int64_t E = FA_TILE_BYTES / SZ;
-  return tstride ? (e0 / E) * tstride + (e0 % E) * SZ : e0 * SZ;
-}
-__device__ __forceinline__ const void* at(const void* p, int64_t ub) { return (const char*)p + ub; }
+// gld / gld_nt / gld_nt_off, MedT, fkey, MSeg, col_base, at: median_common.h (shared with trimmed.hip)
 
 // Rare cases, resolved by an in-order rescan of the column: a NaN anywhere -> ATen returns the
 // FIRST NaN; a zero selected -> the selected rank r falls in the block of (equal) zeros, which ATen

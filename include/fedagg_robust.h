@@ -6,6 +6,8 @@
  *   fa_coord_median     core/security/defense/coordinate_wise_median_defense.py:26-31
  *                       torch.median(torch.cat(client vectors, -1), dim=-1).values
  *   fa_coord_median_tiled  the same over tile-interleaved arena rows
+ *   fa_coord_trimmed_mean, fa_coord_trimmed_mean_tiled  no reference code: the per-coordinate trimmed
+ *                       mean of Yin et al. 2018 (the reference's "trimmed mean" trims whole clients)
  *   fa_pairwise_sqdist  core/security/defense/krum_defense.py:52-66 (_compute_krum_score's
  *                       compute_euclidean_distance(v_i, v_j) ** 2 for every pair)
  *   fa_pairwise_sqdist_rt  the same for bfloat16 / float16 models (differences in the model dtype)
@@ -49,6 +51,32 @@ int fa_coord_median(fa_ctx *ctx, int dtype, int32_t num_segments, const int64_t 
  */
 int fa_coord_median_tiled(fa_ctx *ctx, int dtype, int32_t num_segments, const int64_t *seg_numel, int32_t k,
                           const void *const *d_in, int64_t tile_stride, void *const *d_out, void *hip_stream);
+
+/*
+ * Coordinate-wise trimmed mean (Yin et al. 2018) with trim count `trim` = b, 0 <= b and 2 * b < k
+ * (else FA_ERR_INVALID).  Everything else -- pointer layout d_in[s * k + i], dtypes (F32, BF16, F16,
+ * F64), segment rules, asynchrony on the caller's stream, validation before any HIP call, error
+ * codes -- is fa_coord_median's.  Contract (bit-exact; tests/test_gpu_trimmed_mean.py), for every
+ * element e:
+ *   1. the k values of the column are ordered ascending: -0.0 below +0.0, and NaN (any sign or
+ *      payload) above +inf, as torch.sort / numpy.sort place it; the order of equal values is
+ *      immaterial;
+ *   2. acc = (double)s[b]; acc += (double)s[r] for r = b+1 .. k-1-b, in that order (the sum starts
+ *      FROM the first kept value, not from +0.0: a column of -0.0 yields -0.0);
+ *   3. q = acc / (double)(k - 2 * b);
+ *   4. out[e] = q (F64), (float)q (F32), (dtype)(float)q (BF16, F16: float64 -> float32 -> 16 bits),
+ *      every conversion round-to-nearest-even.
+ * So up to b NaNs per column are trimmed away, a NaN inside the kept window gives NaN (bits
+ * unspecified), as does a kept window holding both +inf and -inf; b = 0 is the unweighted mean in
+ * sorted order, and odd k with b = (k-1)/2 the median's value.  The order of the sum is part of the
+ * contract because a float64 sum of float32 values is not always exact.  Sample counts play no part.
+ */
+int fa_coord_trimmed_mean(fa_ctx *ctx, int dtype, int32_t num_segments, const int64_t *seg_numel, int32_t k,
+                          int32_t trim, const void *const *d_in, void *const *d_out, void *hip_stream);
+/* The same over tile-interleaved client rows (addressing and tile rules of fa_coord_median_tiled). */
+int fa_coord_trimmed_mean_tiled(fa_ctx *ctx, int dtype, int32_t num_segments, const int64_t *seg_numel,
+                                int32_t k, int32_t trim, const void *const *d_in, int64_t tile_stride,
+                                void *const *d_out, void *hip_stream);
 
 /*
  * Pairwise squared Euclidean distances of k float32 client vectors (2 <= k <= 128), each given

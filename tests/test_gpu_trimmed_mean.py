@@ -1,0 +1,394 @@
+"""GPU parity of the coordinate-wise trimmed mean (fa_coord_trimmed_mean, include/fedagg_robust.h):
+bit for bit against a CPU reference that follows the contract -- sort the column (NaN last), sum the
+kept ranks in order in float64 from the first kept value, divide, round once per format -- on every
+network bucket, the one-lane / two-lane boundary, the generic kernel, all dtypes, ragged and unaligned
+segments, the tiled arena layout, hand-made columns, and through ClientArena, the defense class and
+ServerAggregator.
+
+The reference sorts with ``numpy.sort`` and then repairs one thing: ``numpy.sort`` leaves the order of -0.0 and +0.0
+unspecified (they compare equal; its vectorised float32 sort has even been seen to return +0.0 for
+a -0.0 input), and the kept window CAN cut through a block of zeros (odd K with b = (K-1)/2 keeps
+one value; three of the zeros -0, -0, -0, +0 sum to -0 or +0).  ``_order_zeros`` rewrites each sorted
+column's zero block as the column's -0.0s (counted in the unsorted input) followed by its +0.0s, the
+order the contract states (-0.0 below +0.0) and a legitimate result of sorting the column.
+"""
+from __future__ import annotations
+
+import functools
+import types
+from collections import OrderedDict
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+INT_VIEW = {8: torch.int64, 4: torch.int32, 2: torch.int16}
+
+
+@pytest.fixture(scope="module")
+def eng():
+    from fedml_amd.engine import get_engine
+    return get_engine(0)
+
+
+def _order_zeros(s, a):
+    """s: the columns of ``a`` sorted ascending along axis 0 (NaN last).  The zeros of a column are one
+    block that starts after its negatives; give the block's first rows the column's -0.0s."""
+    zero = s == 0
+    start = (s < 0).sum(axis=0)
+    nneg = ((a == 0) & np.signbit(a)).sum(axis=0)
+    r = np.arange(s.shape[0]).reshape((-1,) + (1,) * (s.ndim - 1))
+    s[zero & (r < start + nneg)] = -0.0
+    s[zero & (r >= start + nneg)] = 0.0
+    return s
+
+
+def _sorted_columns(xs):
+    dt = xs[0].dtype
+    a = torch.stack([x.to(torch.float64 if dt == torch.float64 else torch.float32) for x in xs]).numpy()
+    return _order_zeros(np.sort(a, axis=0), a)
+
+
+def _walk(s, b, dt):
+    K = s.shape[0]
+    acc = s[b].astype(np.float64).copy()
+    with np.errstate(all="ignore"):
+        for r in range(b + 1, K - b):
+            acc += s[r].astype(np.float64)
+        q = torch.from_numpy(acc / float(K - 2 * b))
+    return q if dt == torch.float64 else q.to(torch.float32).to(dt)
+
+
+def trimmed_mean_ref(xs, b):
+    return _walk(_sorted_columns(xs), b, xs[0].dtype)
+
+
+def assert_same(got, exp, what=""):
+    got, exp = got.cpu(), exp.cpu()
+    assert got.dtype == exp.dtype and got.shape == exp.shape, what
+    gn, en = torch.isnan(got), torch.isnan(exp)
+    assert torch.equal(gn, en), f"{what}: NaN positions differ in {int((gn != en).sum())} elements"
+    iv = INT_VIEW[got.element_size()]
+    bad = (got.view(iv) != exp.view(iv)) & ~en
+    if bool(bad.any()):
+        i = int(bad.flatten().nonzero()[0])
+        raise AssertionError(f"{what}: {int(bad.sum())} of {got.numel()} elements differ, first at {i}: "
+                             f"got {got.flatten()[i].item()!r}, expected {exp.flatten()[i].item()!r}")
+
+
+def _column_data(g, k, n, dtype, zeros=0.05):
+    xs = []
+    for i in range(k):
+        v = torch.randn(n, generator=g, dtype=torch.float64)
+        u = torch.rand(n, generator=g)
+        v = torch.where(u < zeros, torch.zeros_like(v), v)
+        v = torch.where((u >= zeros) & (u < 2 * zeros), -torch.zeros_like(v), v)
+        v = torch.where((u >= 0.5) & (u < 0.52), torch.round(v * 2) / 2, v)  # ties
+        v = torch.where((u >= 0.9) & (u < 0.901), torch.full_like(v, float("nan")), v)
+        v = torch.where((u >= 0.95) & (u < 0.96), torch.full_like(v, float("inf")) * torch.sign(v - 0.1), v)
+        xs.append(v.to(dtype))
+    return xs
+
+
+@functools.lru_cache(maxsize=4)
+def _case(seed, k, n, dtype, zeros):
+    """(client tensors, their sorted columns): computed once per case, shared by its trim counts."""
+    xs = _column_data(torch.Generator().manual_seed(seed), k, n, dtype, zeros)
+    return xs, _sorted_columns(xs)
+
+
+def _trims(k, cands):
+    return sorted({b for b in cands if 0 <= b and 2 * b < k})
+
+
+# ----------------------------------------------------------------------------- 1. float32, every bucket
+F32_K = [1, 2, 3, 4, 5, 7, 8, 9, 16, 17, 31, 32, 33, 40, 63, 64, 65, 72, 96, 100, 127, 128, 129, 150]
+
+
+@pytest.mark.parametrize("k,b", [(k, b) for k in F32_K for b in _trims(k, [0, 1, k // 10, (k - 1) // 2])])
+def test_trimmed_mean_f32(eng, k, b):
+    n = 3000 if k > 128 else 20001
+    xs, s = _case(k, k, n, torch.float32, 0.05)
+    got = eng.coord_trimmed_mean([[x.to(DEV) for x in xs]], b)[0]
+    assert_same(got, _walk(s, b, torch.float32), f"K={k} b={b}")
+
+
+# ----------------------------------------------------------------------------- 2. dtypes
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float64])
+@pytest.mark.parametrize("k,b", [(k, b) for k in [3, 6, 32, 40, 96] for b in _trims(k, [0, 1, k // 4])])
+def test_trimmed_mean_dtypes(eng, dtype, k, b):
+    xs, s = _case(100 + k, k, 5003, dtype, 0.2)
+    got = eng.coord_trimmed_mean([[x.to(DEV) for x in xs]], b)[0]
+    assert_same(got, _walk(s, b, dtype), f"{dtype} K={k} b={b}")
+
+
+# ----------------------------------------------------------------------------- 3. ragged, unaligned
+@pytest.mark.parametrize("offset", [0, 1])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("k", [2, 8, 17, 33, 65])
+def test_trimmed_mean_ragged_segments(eng, dtype, k, offset):
+    """Six segments in one call, every client tensor and every output a view at an element offset."""
+    b = 1 if 2 < k else 0
+    sizes = [1, 2, 3, 257, 4096, 3001]
+    g = torch.Generator().manual_seed(300 + k)
+    segs_cpu = [_column_data(g, k, n, dtype, zeros=0.1) for n in sizes]
+    view = lambda t: torch.cat([t.new_zeros(offset), t]).to(DEV)[offset:]  # noqa: E731
+    segs = [[view(x) for x in col] for col in segs_cpu]
+    outs = [torch.zeros(n + offset, dtype=dtype, device=DEV)[offset:] for n in sizes]
+    res = eng.coord_trimmed_mean(segs, b, outs=outs)
+    for s, (col, o) in enumerate(zip(segs_cpu, res)):
+        assert o.data_ptr() == outs[s].data_ptr()
+        assert_same(o, trimmed_mean_ref(col, b), f"segment {s} K={k}")
+
+
+# ----------------------------------------------------------------------------- 4. tiled == flat == reference
+def _tiled_rows(xs, dtype, cap_extra=2):
+    """The clients as rows of a tile-interleaved ClientArena group, with spare rows so the row
+    pointers are not the first ``K`` of the capacity."""
+    from fedml_amd.arena import ArenaLayout, ClientArena
+    n = xs[0].numel()
+    arena = ClientArena(ArenaLayout([("w", (n,), dtype)]), len(xs) + cap_extra, device=DEV, tiled=True)
+    rows = list(range(cap_extra, cap_extra + len(xs)))
+    for r, x in zip(rows, xs):
+        arena.write(r, {"w": x.to(DEV)})
+    return arena, rows
+
+
+@pytest.mark.parametrize("small", [False, True], ids=["tiles", "lt_tile"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("k", [5, 33, 64, 100, 128])
+def test_trimmed_mean_tiled_equals_flat(eng, dtype, k, small):
+    b = k // 10
+    per_tile = 4096 // (4 if dtype == torch.float32 else 2)
+    n = 500 if small else 2 * per_tile + 777
+    g = torch.Generator().manual_seed(400 + k)
+    xs = _column_data(g, k, n, dtype, zeros=0.15)
+    arena, rows = _tiled_rows(xs, dtype)
+    exp = trimmed_mean_ref(xs, b)
+    got = eng.coord_trimmed_mean_tiled(arena.bufs[dtype], rows, b, n=n)
+    assert_same(got, exp, "tiled")
+    assert_same(eng.coord_trimmed_mean([[x.to(DEV) for x in xs]], b)[0], exp, "flat")
+    # a row subset in another order: the result does not depend on the client order
+    perm = torch.randperm(k, generator=g).tolist()[:max(1, k - 2)]
+    bs = min(b, (len(perm) - 1) // 2)
+    exp = trimmed_mean_ref([xs[i] for i in perm], bs)
+    assert_same(eng.coord_trimmed_mean_tiled(arena.bufs[dtype], [rows[i] for i in perm], bs, n=n), exp, "tiled subset")
+    assert_same(eng.coord_trimmed_mean([[xs[i].to(DEV) for i in perm]], bs)[0], exp, "flat subset")
+
+
+# ----------------------------------------------------------------------------- 5. directed columns
+NEG_NAN = torch.tensor([-4194304], dtype=torch.int32).view(torch.float32).item()  # 0xFFC00000
+
+
+def _directed(k, b):
+    """name -> the column's K values (ascending where it matters; the test shuffles the clients)."""
+    nan, inf = float("nan"), float("inf")
+    fin = [0.25 * i - 3.0 for i in range(k)]
+    third = k // 3
+    return OrderedDict([
+        ("b_nans", fin[:k - b] + [nan] * b),
+        ("b_plus_1_nans", fin[:k - b - 1] + [nan] * (b + 1)),
+        ("negative_nan", fin[:k - 1] + [NEG_NAN]),
+        ("negative_nans_b", fin[:k - b] + [NEG_NAN] * b),
+        ("negative_nans_b_plus_1", fin[:k - b - 1] + [NEG_NAN] * (b + 1)),
+        ("both_infs_kept", [-inf] * (b + 1) + fin[:k - 2 * b - 2] + [inf] * (b + 1)),
+        ("infs_trimmed", [-inf] * b + fin[:k - 2 * b] + [inf] * b),
+        ("all_neg_zero", [-0.0] * k),
+        ("mixed_zeros", [-0.0] * (k // 2) + [0.0] * (k - k // 2)),
+        ("all_equal", [1.7] * k),
+        ("huge_and_tiny", [-1e30] * third + [1e-30] * (k - 2 * third) + [1e30] * third),
+    ])
+
+
+@pytest.mark.parametrize("k,b", [(9, 2), (100, 10)])
+def test_trimmed_mean_directed_columns(eng, k, b):
+    cols = _directed(k, b)
+    g = torch.Generator().manual_seed(k)
+    m = torch.tensor(list(cols.values()), dtype=torch.float32).t().contiguous()  # [K, columns]
+    for c in range(m.shape[1]):  # the clients' order must not matter
+        m[:, c] = m[torch.randperm(k, generator=g), c]
+    m = m.repeat(1, 40)  # more than one wave of columns
+    xs = [m[i].contiguous() for i in range(k)]
+    assert int(torch.isnan(m).sum()) > 0 and bool((m.view(torch.int32) == -4194304).any())
+    got = eng.coord_trimmed_mean([[x.to(DEV) for x in xs]], b)[0].cpu()
+    assert_same(got, trimmed_mean_ref(xs, b), f"K={k} b={b}")
+    res = dict(zip(cols, got[:len(cols)]))
+    for name in ("b_nans", "negative_nan", "negative_nans_b", "infs_trimmed", "huge_and_tiny"):
+        assert bool(torch.isfinite(res[name])), name
+    for name in ("b_plus_1_nans", "negative_nans_b_plus_1", "both_infs_kept"):
+        assert bool(torch.isnan(res[name])), name
+    bits = lambda t: int(t.view(torch.int32))  # noqa: E731
+    assert bits(res["all_neg_zero"]) == -2 ** 31
+    assert bits(res["mixed_zeros"]) == 0
+    assert bits(res["all_equal"]) == bits(torch.tensor(1.7, dtype=torch.float32))  # the sum of <= 80 copies is exact
+
+
+# ----------------------------------------------------------------------------- 6. against the median
+@pytest.mark.parametrize("k", [3, 33, 127])
+def test_trimmed_mean_full_trim_is_the_median(eng, k):
+    xs, _ = _case(600 + k, k, 20001, torch.float32, 0.05)
+    dev = [x.to(DEV) for x in xs]
+    tm = eng.coord_trimmed_mean([dev], (k - 1) // 2)[0].cpu()
+    med = eng.coord_median([dev])[0].cpu()
+    clean = ~torch.isnan(torch.stack(xs)).any(dim=0)
+    assert int(clean.sum()) > 1000
+    assert bool((tm[clean] == med[clean]).all())  # by value: the sign of a selected zero may differ
+
+
+# ----------------------------------------------------------------------------- 7. ClientArena.trimmed_mean
+@pytest.mark.parametrize("tiled", [False, True])
+def test_arena_trimmed_mean_per_key(eng, tiled):
+    from fedml_amd.arena import ArenaLayout, ClientArena
+    g = torch.Generator().manual_seed(12)
+    shapes = [("conv.weight", (16, 3, 3, 3), torch.float32), ("conv.bias", (16,), torch.float32),
+              ("emb.weight", (37, 29), torch.bfloat16), ("fc.weight", (10, 300), torch.float32),
+              ("emb.scale", (29,), torch.bfloat16)]
+    K, b = 12, 2
+    ds = [OrderedDict((k, _column_data(g, 1, int(np.prod(s)), dt)[0].view(s)) for k, s, dt in shapes) for _ in range(K)]
+    arena = ClientArena(ArenaLayout(shapes), K + 1, device=DEV, tiled=tiled)
+    assert set(arena.bufs) == {torch.float32, torch.bfloat16}
+    for i, d in enumerate(ds):
+        arena.write(i + 1, OrderedDict((k, v.to(DEV)) for k, v in d.items()))
+    tm = arena.trimmed_mean(b, list(range(1, K + 1)))
+    assert list(tm) == [k for k, _, _ in shapes]
+    for k, s, dt in shapes:
+        assert tm[k].shape == torch.Size(s) and tm[k].dtype == dt
+        assert_same(tm[k].reshape(-1), trimmed_mean_ref([d[k].reshape(-1) for d in ds], b), k)
+
+
+# ----------------------------------------------------------------------------- 8. the defense
+MODEL = [("conv.weight", (8, 3, 3, 3)), ("bn.weight", (8,)), ("bn.bias", (8,)), ("bn.running_mean", (8,)),
+         ("bn.running_var", (8,)), ("bn.num_batches_tracked", ()), ("fc.weight", (10, 50)), ("fc.bias", (10,))]
+COUNTS = [10, 20, 30, 40, 50, 60, 70, 80, 90, 100]
+
+
+def _client_dicts(K=10, ints=True, where="cpu"):
+    g = torch.Generator().manual_seed(77)
+    ds = []
+    for i in range(K):
+        d = OrderedDict()
+        for k, s in MODEL:
+            if k.endswith("num_batches_tracked"):
+                if ints:
+                    d[k] = torch.tensor(100 + 7 * i, dtype=torch.int64)
+            else:
+                d[k] = _column_data(g, 1, int(np.prod(s)), torch.float32)[0].view(s)
+        ds.append(OrderedDict((k, v.to(DEV) if where == "cuda" else v) for k, v in d.items()))
+    return ds
+
+
+def _snapshot(ds):
+    return [OrderedDict((k, v.detach().cpu().clone()) for k, v in d.items()) for d in ds]
+
+
+def _assert_unchanged(ds, snap):
+    for d, s in zip(ds, snap):
+        assert list(d) == list(s)
+        for k in s:
+            assert torch.equal(d[k].cpu().view(INT_VIEW[s[k].element_size()]), s[k].view(INT_VIEW[s[k].element_size()])), k
+
+
+def _check_defended(out, ds, snap, b, where):
+    from fedml_amd.ml.aggregator.agg_operator import FedMLAggOperator
+    assert isinstance(out, OrderedDict) and all(out is not d for d in ds)
+    assert list(out) == list(ds[0])
+    base = FedMLAggOperator.agg(types.SimpleNamespace(federated_optimizer="FedAvg"), list(zip(COUNTS, ds)))
+    for k, v in out.items():
+        assert v.device == ds[0][k].device and v.device.type == where, k
+        assert v.shape == ds[0][k].shape, k
+        if ds[0][k].dtype == torch.int64:  # the base aggregation's value (FedAvg: int * float -> float32)
+            assert v.dtype == base[k].dtype and torch.equal(v.cpu(), base[k].cpu()), k
+        else:
+            assert v.dtype == ds[0][k].dtype, k
+            assert_same(v.reshape(-1), trimmed_mean_ref([s[k].reshape(-1) for s in snap], b), k)
+    _assert_unchanged(ds, snap)
+
+
+@pytest.mark.parametrize("where", ["cpu", "cuda"])
+def test_defense_on_state_dicts(where):
+    from fedml_amd.core.security.defense.coordinate_trimmed_mean_defense import CoordinateTrimmedMeanDefense
+    from fedml_amd.ml.aggregator.agg_operator import FedMLAggOperator
+    ds = _client_dicts(where=where)
+    snap = _snapshot(ds)
+    d = CoordinateTrimmedMeanDefense(types.SimpleNamespace(beta=0.2, federated_optimizer="FedAvg"))
+    out = d.defend_on_aggregation(list(zip(COUNTS, ds)), base_aggregation_func=FedMLAggOperator.agg)
+    _check_defended(out, ds, snap, 2, where)
+    with pytest.raises(TypeError):  # an int64 key and nothing to aggregate it with
+        d.defend_on_aggregation(list(zip(COUNTS, ds)))
+    _assert_unchanged(ds, snap)
+
+
+def _reset_defender():
+    from fedml_amd.core.security.fedml_defender import FedMLDefender
+    FedMLDefender.get_instance().init(types.SimpleNamespace())
+
+
+@pytest.mark.parametrize("where", ["cpu", "cuda"])
+def test_defense_through_server_aggregator(where):
+    from fedml_amd.ml.aggregator.default_aggregator import DefaultServerAggregator
+    ds = _client_dicts(where=where)
+    snap = _snapshot(ds)
+    try:
+        agg = DefaultServerAggregator(torch.nn.Linear(50, 10), types.SimpleNamespace(
+            enable_defense=True, defense_type="coordinate_trimmed_mean", beta=0.2, federated_optimizer="FedAvg"))
+        raw = list(zip(COUNTS, ds))
+        kept, idxs = agg.on_before_aggregation(raw)
+        assert len(kept) == len(raw) and all(a is b for (_, a), (_, b) in zip(kept, raw))
+        assert idxs == list(range(len(ds)))
+        out = agg.aggregate(kept)
+    finally:
+        _reset_defender()
+    _check_defended(out, ds, snap, 2, where)
+
+
+@pytest.mark.parametrize("ints", [False, True], ids=["float_only", "with_int_key"])
+def test_defense_on_adopted_rows(ints, monkeypatch):
+    """Updates adopted into one arena's rows: float groups only take ClientArena.trimmed_mean (one
+    launch per group over the rows); with an int64 group the per-key path runs.  Same bits either way."""
+    from fedml_amd.arena import ClientArena, resident_rows
+    from fedml_amd.core.security.defense.coordinate_trimmed_mean_defense import CoordinateTrimmedMeanDefense
+    from fedml_amd.ml.aggregator.agg_operator import FedMLAggOperator
+    ds = _client_dicts(ints=ints, where="cuda")
+    snap = _snapshot(ds)
+    arena = ClientArena.for_model(ds[0], len(ds), device=DEV)
+    for i, d in enumerate(ds):
+        arena.adopt(i, d)
+    assert resident_rows(ds) is not None
+    calls = []
+    real = ClientArena.trimmed_mean
+    monkeypatch.setattr(ClientArena, "trimmed_mean", lambda self, *a, **kw: calls.append(a) or real(self, *a, **kw))
+    d = CoordinateTrimmedMeanDefense(types.SimpleNamespace(beta=0.2, federated_optimizer="FedAvg"))
+    out = d.defend_on_aggregation(list(zip(COUNTS, ds)), base_aggregation_func=FedMLAggOperator.agg)
+    assert len(calls) == (0 if ints else 1)
+    _check_defended(out, ds, snap, 2, "cuda")
+
+
+# ----------------------------------------------------------------------------- 9. errors
+def test_trimmed_mean_errors(eng):
+    from fedml_amd import _native as N
+    K, n = 6, 100
+    xs = [torch.randn(n, device=DEV) for _ in range(K)]
+    for bad in (-1, 3):
+        with pytest.raises(ValueError):
+            eng.coord_trimmed_mean([xs], bad)
+    with pytest.raises(TypeError):
+        eng.coord_trimmed_mean([[x.to(torch.int64) for x in xs]], 1)
+    arena, rows = _tiled_rows([x.cpu() for x in xs], torch.float32)
+    for bad in (-1, 3):
+        with pytest.raises(ValueError):
+            eng.coord_trimmed_mean_tiled(arena.bufs[torch.float32], rows, bad, n=n)
+    with pytest.raises(TypeError):
+        eng.coord_trimmed_mean_tiled(torch.zeros(1, K, 512, dtype=torch.int64, device=DEV), list(range(K)), 1)
+    out = torch.full((n,), 7.0, device=DEV)
+    L = N.lib()
+    ptrs, outp = N.ptr_array([x.data_ptr() for x in xs]), N.ptr_array([out.data_ptr()])
+    for bad in (-1, 3):
+        rc = L.fa_coord_trimmed_mean(eng._ctx, N.F32, 1, N.i64_array([n]), K, bad, ptrs, outp, None)
+        assert rc == N.FA_ERR_INVALID and b"trim" in L.fa_last_error()
+        rc = L.fa_coord_trimmed_mean_tiled(eng._ctx, N.F32, 1, N.i64_array([n]), K, bad, ptrs, 4096, outp, None)
+        assert rc == N.FA_ERR_INVALID and b"trim" in L.fa_last_error()
+    torch.cuda.synchronize()
+    assert bool((out == 7.0).all())  # nothing was launched
