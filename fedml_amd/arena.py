@@ -480,6 +480,26 @@ class ClientArena:
                 outs[dt] = self.engine.weighted_sum_rows(buf, clients, mode, coef, divisor, out=o)
         return self.layout.carve(outs)
 
+    def _column_op(self, what: str, clients, no_clients: Exception, out, *trim) -> "OrderedDict[str, torch.Tensor]":
+        """median / trimmed_mean: the engine's coord_<what>[_tiled] over every dtype group."""
+        clients = list(range(self.capacity)) if clients is None else list(clients)
+        if not clients:
+            raise no_clients
+        if any(dt not in (torch.float32, torch.bfloat16, torch.float16, torch.float64) for dt in self.bufs):
+            raise TypeError(f"{what}: the arena holds a non-float dtype group")
+        self._wait_ingest()
+        outs: Dict[torch.dtype, torch.Tensor] = {}
+        for dt, buf in self.bufs.items():
+            o = out[dt] if out is not None else None
+            n = self.layout.group_numel[dt]
+            if self.tiled:
+                outs[dt] = getattr(self.engine, f"coord_{what}_tiled")(buf, clients, *trim, n=n, out=o)
+            else:
+                o = o if o is not None else torch.empty(n, dtype=dt, device=buf.device)
+                getattr(self.engine, f"coord_{what}")([[buf[i][:n] for i in clients]], *trim, outs=[o])
+                outs[dt] = o
+        return self.layout.carve(outs)
+
     def median(self, clients: Optional[Sequence[int]] = None,
                out: Optional[Dict[torch.dtype, torch.Tensor]] = None) -> "OrderedDict[str, torch.Tensor]":
         """Coordinate-wise median over the given client rows (default: all), one launch per dtype
@@ -487,23 +507,8 @@ class ClientArena:
         selection, bit for bit): tiled arenas through fa_coord_median_tiled (the layout whose K tiles
         of a workgroup are one contiguous run), client-major arenas over the row views.  Float groups
         only (the reference's median runs over weight tensors).  Returns per-key views."""
-        clients = list(range(self.capacity)) if clients is None else list(clients)
-        if not clients:
-            raise RuntimeError("torch.cat(): expected a non-empty list of Tensors")
-        if any(dt not in (torch.float32, torch.bfloat16, torch.float16, torch.float64) for dt in self.bufs):
-            raise TypeError("median: the arena holds a non-float dtype group")
-        self._wait_ingest()
-        outs: Dict[torch.dtype, torch.Tensor] = {}
-        for dt, buf in self.bufs.items():
-            o = out[dt] if out is not None else None
-            n = self.layout.group_numel[dt]
-            if self.tiled:
-                outs[dt] = self.engine.coord_median_tiled(buf, clients, n=n, out=o)
-            else:
-                o = o if o is not None else torch.empty(n, dtype=dt, device=buf.device)
-                self.engine.coord_median([[buf[i][:n] for i in clients]], outs=[o])
-                outs[dt] = o
-        return self.layout.carve(outs)
+        return self._column_op("median", clients,
+                               RuntimeError("torch.cat(): expected a non-empty list of Tensors"), out)
 
     def trimmed_mean(self, trim: int, clients: Optional[Sequence[int]] = None,
                      out: Optional[Dict[torch.dtype, torch.Tensor]] = None) -> "OrderedDict[str, torch.Tensor]":
@@ -511,23 +516,7 @@ class ClientArena:
         client rows (default: all) with ``trim`` values dropped at each end of every column, one launch
         per dtype group: tiled arenas through fa_coord_trimmed_mean_tiled, client-major arenas over the
         row views.  Float groups only.  Returns per-key views."""
-        clients = list(range(self.capacity)) if clients is None else list(clients)
-        if not clients:
-            raise ValueError("trimmed_mean: no client rows")
-        if any(dt not in (torch.float32, torch.bfloat16, torch.float16, torch.float64) for dt in self.bufs):
-            raise TypeError("trimmed_mean: the arena holds a non-float dtype group")
-        self._wait_ingest()
-        outs: Dict[torch.dtype, torch.Tensor] = {}
-        for dt, buf in self.bufs.items():
-            o = out[dt] if out is not None else None
-            n = self.layout.group_numel[dt]
-            if self.tiled:
-                outs[dt] = self.engine.coord_trimmed_mean_tiled(buf, clients, trim, n=n, out=o)
-            else:
-                o = o if o is not None else torch.empty(n, dtype=dt, device=buf.device)
-                self.engine.coord_trimmed_mean([[buf[i][:n] for i in clients]], trim, outs=[o])
-                outs[dt] = o
-        return self.layout.carve(outs)
+        return self._column_op("trimmed_mean", clients, ValueError("trimmed_mean: no client rows"), out, trim)
 
     def _pair_groups(self) -> Optional[torch.dtype]:
         """The float dtype when the arena holds exactly one float group and one int64 group."""

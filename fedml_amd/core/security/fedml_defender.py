@@ -3,8 +3,8 @@ robust aggregators of this engine: krum / multikrum, trimmed_mean, wise_median a
 coordinate_trimmed_mean (the per-coordinate trimmed mean of Yin et al. 2018, which the reference
 lacks: its trimmed_mean trims whole clients and keeps that meaning here).  Same dispatch
 (which defenses act before / on / after aggregation) and the same entry points; the per-element work
-runs in the HIP kernels (fedml_amd/csrc/robust.hip, trimmed.hip).  Other defense types of the reference are
-outside the aggregation path and raise NotImplementedError when configured.
+runs in the HIP kernels (fedml_amd/csrc/median.hip, trimmed.hip, robust.hip).  Other defense types of
+the reference are outside the aggregation path and raise NotImplementedError when configured.
 """
 from __future__ import annotations
 

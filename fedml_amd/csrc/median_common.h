@@ -1,7 +1,8 @@
 // median_common.h -- device helpers shared by the per-column kernels of the robust family
-// (robust.hip: coordinate-wise median; trimmed.hip: coordinate-wise trimmed mean): raw global loads,
-// the 16-bit types' exact widening to float, the order-preserving float key, the segment record and
-// the flat / tile-interleaved column addressing.  Not part of the ABI.
+// (median.hip: coordinate-wise median; trimmed.hip: coordinate-wise trimmed mean): raw global loads,
+// the 16-bit types' exact widening to float, the order-preserving float key, the segment record,
+// the flat / tile-interleaved column addressing.  Their common host path is median_host.h.  Not part
+// of the ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -39,7 +40,6 @@ template <> struct MedT<FA_DTYPE_F32> {
   __device__ static float load(const void* p, int64_t e) { return gld_nt<float>(p, e); }
   __device__ static float load_off(const void* p, unsigned off) { return gld_nt_off<float>(p, off); }
   __device__ static void store(void* p, int64_t e, float v) { ((float*)p)[e] = v; }
-  __device__ static void store_bits(void* p, int64_t e, const void* src) { ((unsigned*)p)[e] = ((const unsigned*)src)[e]; }
   __device__ static void store_bits_off(void* p, int64_t e, const void* src, unsigned off) {
     ((unsigned*)p)[e] = gld_nt_off<unsigned>(src, off);
   }
@@ -55,9 +55,6 @@ template <> struct MedT<FA_DTYPE_BF16> {
   __device__ static void store(void* p, int64_t e, float v) {
     ((unsigned short*)p)[e] = (unsigned short)(__float_as_uint(v) >> 16);  // exact: v came from bf16
   }
-  __device__ static void store_bits(void* p, int64_t e, const void* src) {
-    ((unsigned short*)p)[e] = ((const unsigned short*)src)[e];
-  }
   __device__ static void store_bits_off(void* p, int64_t e, const void* src, unsigned off) {
     ((unsigned short*)p)[e] = gld_nt_off<unsigned short>(src, off);
   }
@@ -72,9 +69,6 @@ template <> struct MedT<FA_DTYPE_F16> {
   }
   __device__ static void store(void* p, int64_t e, float v) {
     ((unsigned short*)p)[e] = __builtin_bit_cast(unsigned short, (_Float16)v);  // exact: v came from f16
-  }
-  __device__ static void store_bits(void* p, int64_t e, const void* src) {
-    ((unsigned short*)p)[e] = ((const unsigned short*)src)[e];
   }
   __device__ static void store_bits_off(void* p, int64_t e, const void* src, unsigned off) {
     ((unsigned short*)p)[e] = gld_nt_off<unsigned short>(src, off);
@@ -113,5 +107,14 @@ __device__ __forceinline__ int64_t col_base(int64_t e0, int64_t tstride) {
   return tstride ? (e0 / E) * tstride + (e0 % E) * SZ : e0 * SZ;
 }
 __device__ __forceinline__ const void* at(const void* p, int64_t ub) { return (const char*)p + ub; }
+
+// float64 has no MedT (no network runs on it): its element size, and any dtype's element
+// at(p, ub) + lane offset c (elements) widened exactly to double, for the in-order kernels
+template <int DT> constexpr int elem_bytes() { if constexpr (DT == FA_DTYPE_F64) return 8; else return MedT<DT>::kBytes; }
+template <int DT>
+__device__ __forceinline__ double load_d(const void* p, int64_t c) {
+  if constexpr (DT == FA_DTYPE_F64) return gld<double>(p, c);
+  else return (double)MedT<DT>::load(p, c);
+}
 
 }  // namespace fa_detail

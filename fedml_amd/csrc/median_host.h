@@ -1,0 +1,93 @@
+// median_host.h -- the host path shared by the C entries of the per-column operators (median.hip,
+// trimmed.hip): argument checks, the grid for a given columns-per-workgroup, the MSeg + pointer table
+// in a staging slot, and the launch.  An entry checks in this order: col_check_args (NULL context,
+// then the other arguments), its own arguments (the trim), col_launch (dtype, then tile_stride).
+// Not part of the ABI.
+#pragma once
+
+#include "fa_internal.h"
+#include "median_common.h"
+
+namespace fa_detail {
+
+// The arguments every per-column entry takes; fn is the entry's name for the messages.
+struct ColArgs {
+  const char* fn;
+  fa_ctx* ctx;
+  int dtype;
+  int32_t num_segments;
+  const int64_t* seg_numel;
+  int32_t k;
+  const void* const* d_in;  // [num_segments][k]
+  int64_t tstride;          // 0: flat segments; > 0: tile-interleaved inputs
+  void* const* d_out;
+  void* hip_stream;
+};
+
+inline int col_check_args(const ColArgs& a) {
+  if (!a.ctx) return fail(FA_ERR_INVALID, "%s: ctx is NULL", a.fn);
+  if (a.k <= 0 || a.num_segments <= 0 || !a.seg_numel || !a.d_in || !a.d_out)
+    return fail(FA_ERR_INVALID, "%s: invalid arguments", a.fn);
+  return FA_OK;
+}
+
+// Checks the dtype, the tile stride and every non-empty segment's pointers, stages the segment and
+// pointer tables (skipped when the slot already holds them) and calls
+// launch(grid, stream, segs, nseg, ptrs) with `cols` columns per workgroup -- a count that divides
+// a tile's element count (512 float64 at the least), so no workgroup straddles a tile.
+template <class Launch>
+int col_launch(const ColArgs& a, int64_t cols, Launch launch) {
+  const int k = a.k;
+  if (a.dtype != FA_DTYPE_F32 && a.dtype != FA_DTYPE_BF16 && a.dtype != FA_DTYPE_F16 && a.dtype != FA_DTYPE_F64)
+    return fail(FA_ERR_DTYPE, "%s: dtype %d not supported (F32, BF16, F16, F64)", a.fn, a.dtype);
+  if (a.tstride < 0 || a.tstride % FA_TILE_BYTES)
+    return fail(FA_ERR_INVALID, "%s: tile_stride must be a positive multiple of %d (got %lld)", a.fn, FA_TILE_BYTES,
+                (long long)a.tstride);
+  int nseg = 0;
+  int64_t tiles = 0;
+  for (int s = 0; s < a.num_segments; ++s) {
+    if (a.seg_numel[s] < 0) return fail(FA_ERR_INVALID, "%s: segment %d has negative numel", a.fn, s);
+    if (a.seg_numel[s] == 0) continue;
+    if (!a.d_out[s]) return fail(FA_ERR_INVALID, "%s: segment %d: output NULL", a.fn, s);
+    for (int i = 0; i < k; ++i)
+      if (!a.d_in[(int64_t)s * k + i])
+        return fail(FA_ERR_INVALID, "%s: segment %d client %d: input NULL", a.fn, s, i);
+    ++nseg;
+    tiles += (a.seg_numel[s] + cols - 1) / cols;
+  }
+  if (nseg == 0) return FA_OK;
+  if (tiles > 0x7FFFFFFFll) return fail(FA_ERR_INVALID, "%s: too many tiles", a.fn);
+  const size_t seg_bytes = align16(sizeof(MSeg) * nseg);
+  const size_t ptr_bytes = sizeof(void*) * (size_t)nseg * k;
+  DeviceGuard g(a.ctx->device);
+  if (!g.ok) return fail(FA_ERR_HIP, "hipSetDevice(%d) failed", a.ctx->device);
+  hipStream_t st = (hipStream_t)a.hip_stream;
+  fa_ctx::Slot* slot = nullptr;
+  int rc = acquire_slot(a.ctx, seg_bytes + ptr_bytes, &slot);
+  if (rc) return rc;
+  char* h = (char*)slot->host;
+  MSeg* hs = (MSeg*)h;
+  const void** hp = (const void**)(h + seg_bytes);
+  int j = 0;
+  int64_t t0 = 0;
+  for (int s = 0; s < a.num_segments; ++s) {
+    const int64_t n = a.seg_numel[s];
+    if (n == 0) continue;
+    for (int i = 0; i < k; ++i) hp[(int64_t)j * k + i] = a.d_in[(int64_t)s * k + i];
+    hs[j] = MSeg{n, t0, a.d_out[s], a.tstride, j * k, 0};
+    t0 += (n + cols - 1) / cols;
+    ++j;
+  }
+  rc = stage(slot, seg_bytes + ptr_bytes, st, true);
+  if (rc) return rc;
+  const char* dv = (const char*)slot->dev;
+  launch(dim3((unsigned)tiles), st, (const MSeg*)dv, nseg, (const void* const*)(dv + seg_bytes));
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    (void)release(slot, st);
+    return fail(FA_ERR_HIP, "%s: %s", a.fn, hipGetErrorString(e));
+  }
+  return release(slot, st);
+}
+
+}  // namespace fa_detail

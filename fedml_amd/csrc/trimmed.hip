@@ -6,9 +6,9 @@
 // divide by K - 2b, round once to float32 (and once more to bf16 / f16).  The sum's order is part of
 // the contract: a float64 sum of float32 values is not always exact.
 //
-// Same family as the median kernels (robust.hip), whose helpers (median_common.h), sorting networks
-// (median_nets.h) and addressing it shares; here the network is a FULL sort, since every kept rank is
-// needed.  The float networks run on IEEE 754-2019 minimum / maximum: -0 < +0, and one NaN turns every
+// Same family as the median kernels (median.hip), whose helpers (median_common.h), host path
+// (median_host.h), sorting networks (median_nets.h) and addressing it shares; here the network is a
+// FULL sort, since every kept rank is needed.  The float networks run on IEEE 754-2019 minimum / maximum: -0 < +0, and one NaN turns every
 // output NaN -- so a NaN result (a NaN in the column, or +inf and -inf both kept) sends that column to
 // the in-order path trimmed_col(), which places NaNs as the largest values.
 //   K <= 64          k_tmean_off: one lane per coordinate, B = K rounded up to 8 keys in registers
@@ -21,20 +21,12 @@
 #include "fa_internal.h"
 #include "fedagg_robust.h"
 #include "median_common.h"
+#include "median_host.h"
 #include "trimmed_nets.h"
 
 using namespace fa_detail;
 
 namespace {
-
-template <int DT> constexpr int tm_bytes() { if constexpr (DT == FA_DTYPE_F64) return 8; else return MedT<DT>::kBytes; }
-
-// client element at(p, ub) + lane offset c (elements), widened exactly to double
-template <int DT>
-__device__ __forceinline__ double tm_load(const void* p, int64_t c) {
-  if constexpr (DT == FA_DTYPE_F64) return gld<double>(p, c);
-  else return (double)MedT<DT>::load(p, c);
-}
 
 // q -> out[e]: float64 as is; float32 one rounding; bf16 / f16 float64 -> float32 -> 16 bits, each
 // round-to-nearest-even (what torch's q.to(float32).to(dtype) does)
@@ -75,7 +67,7 @@ __device__ double trimmed_col(const void* const* in, int64_t ub, int64_t c, int 
     int bi = -1;
     double bv = 0.0;
     for (int j = 0; j < k; ++j) {
-      const double v = tm_load<DT>(at(in[j], ub), c);
+      const double v = load_d<DT>(at(in[j], ub), c);
       const unsigned long long kj = dkey(v);
       const bool after = r == 0 || kj > ck || (kj == ck && j > ci);
       if (after && (bi < 0 || kj < bk)) { bk = kj; bi = j; bv = v; }
@@ -226,7 +218,7 @@ k_tmean_rank(const MSeg* __restrict__ segs, int nseg, const void* const* __restr
   const int64_t e0 = (tile - sg.tile_start) * kBlock, e = e0 + threadIdx.x;
   if (e >= sg.numel) return;
   const void* const* in = ptrs + sg.ptr_base;
-  const int64_t ub = col_base<tm_bytes<DT>()>(e0, sg.tstride);
+  const int64_t ub = col_base<elem_bytes<DT>()>(e0, sg.tstride);
   const double acc = trimmed_col<DT>(in, ub, e - e0, k, b);
   tm_store<DT>(sg.out, e, acc / (double)(k - 2 * b));
 }
@@ -252,73 +244,20 @@ void launch_tmean(int k, int b, dim3 grid, hipStream_t st, const MSeg* ds, int n
   hipLaunchKernelGGL((k_tmean_rank<DT>), grid, dim3(kBlock), 0, st, ds, nseg, dp, k, b);
 }
 
-// Grid, segment table and slot staging as median_impl (robust.hip).
-int tmean_impl(const char* fn, fa_ctx* ctx, int dtype, int32_t num_segments, const int64_t* seg_numel, int32_t k,
-               int32_t trim, const void* const* d_in, int64_t tstride, void* const* d_out, void* hip_stream) {
-  if (!ctx) return fail(FA_ERR_INVALID, "ctx is NULL");
-  if (k <= 0 || num_segments <= 0 || !seg_numel || !d_in || !d_out)
-    return fail(FA_ERR_INVALID, "%s: invalid arguments", fn);
+int tmean_impl(const ColArgs& a, int32_t trim) {
+  if (const int rc = col_check_args(a)) return rc;
+  const int k = a.k;
   if (trim < 0 || 2 * (int64_t)trim >= k)
-    return fail(FA_ERR_INVALID, "%s: trim must satisfy 0 <= trim and 2 * trim < k (trim %d, k %d)", fn, trim, k);
-  if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_BF16 && dtype != FA_DTYPE_F16 && dtype != FA_DTYPE_F64)
-    return fail(FA_ERR_DTYPE, "%s: dtype %d not supported (F32, BF16, F16, F64)", fn, dtype);
-  if (tstride < 0 || tstride % FA_TILE_BYTES)
-    return fail(FA_ERR_INVALID, "%s: tile_stride must be a positive multiple of %d (got %lld)", fn, FA_TILE_BYTES,
-                (long long)tstride);
-  // columns per workgroup: 256 or 128, both divide a tile's element count (512 float64 at the least)
-  const int64_t tile_elems = tmean_lanes(dtype, k) == 2 ? kTm2lCols : kBlock;
-  int nseg = 0;
-  int64_t tiles = 0;
-  for (int s = 0; s < num_segments; ++s) {
-    if (seg_numel[s] < 0) return fail(FA_ERR_INVALID, "segment %d has negative numel", s);
-    if (seg_numel[s] == 0) continue;
-    if (!d_out[s]) return fail(FA_ERR_INVALID, "segment %d: output NULL", s);
-    for (int i = 0; i < k; ++i)
-      if (!d_in[(int64_t)s * k + i]) return fail(FA_ERR_INVALID, "segment %d client %d: input NULL", s, i);
-    ++nseg;
-    tiles += (seg_numel[s] + tile_elems - 1) / tile_elems;
-  }
-  if (nseg == 0) return FA_OK;
-  if (tiles > 0x7FFFFFFFll) return fail(FA_ERR_INVALID, "too many tiles");
-  const size_t seg_bytes = align16(sizeof(MSeg) * nseg);
-  const size_t ptr_bytes = sizeof(void*) * (size_t)nseg * k;
-  DeviceGuard g(ctx->device);
-  if (!g.ok) return fail(FA_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
-  hipStream_t st = (hipStream_t)hip_stream;
-  fa_ctx::Slot* slot = nullptr;
-  int rc = acquire_slot(ctx, seg_bytes + ptr_bytes, &slot);
-  if (rc) return rc;
-  char* h = (char*)slot->host;
-  MSeg* hs = (MSeg*)h;
-  const void** hp = (const void**)(h + seg_bytes);
-  int j = 0;
-  int64_t t0 = 0;
-  for (int s = 0; s < num_segments; ++s) {
-    const int64_t n = seg_numel[s];
-    if (n == 0) continue;
-    for (int i = 0; i < k; ++i) hp[(int64_t)j * k + i] = d_in[(int64_t)s * k + i];
-    hs[j] = MSeg{n, t0, d_out[s], tstride, j * k, 0};
-    t0 += (n + tile_elems - 1) / tile_elems;
-    ++j;
-  }
-  rc = stage(slot, seg_bytes + ptr_bytes, st, true);
-  if (rc) return rc;
-  const char* dv = (const char*)slot->dev;
-  const MSeg* ds = (const MSeg*)dv;
-  const void* const* dp = (const void* const*)(dv + seg_bytes);
-  const dim3 grid((unsigned)tiles);
-  switch (dtype) {
-    case FA_DTYPE_F32: launch_tmean<FA_DTYPE_F32>(k, trim, grid, st, ds, nseg, dp); break;
-    case FA_DTYPE_BF16: launch_tmean<FA_DTYPE_BF16>(k, trim, grid, st, ds, nseg, dp); break;
-    case FA_DTYPE_F16: launch_tmean<FA_DTYPE_F16>(k, trim, grid, st, ds, nseg, dp); break;
-    default: launch_tmean<FA_DTYPE_F64>(k, trim, grid, st, ds, nseg, dp); break;
-  }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    (void)release(slot, st);
-    return fail(FA_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
-  }
-  return release(slot, st);
+    return fail(FA_ERR_INVALID, "%s: trim must satisfy 0 <= trim and 2 * trim < k (trim %d, k %d)", a.fn, trim, k);
+  return col_launch(a, tmean_lanes(a.dtype, k) == 2 ? kTm2lCols : kBlock,
+                    [&](dim3 grid, hipStream_t st, const MSeg* ds, int nseg, const void* const* dp) {
+                      switch (a.dtype) {
+                        case FA_DTYPE_F32: launch_tmean<FA_DTYPE_F32>(k, trim, grid, st, ds, nseg, dp); break;
+                        case FA_DTYPE_BF16: launch_tmean<FA_DTYPE_BF16>(k, trim, grid, st, ds, nseg, dp); break;
+                        case FA_DTYPE_F16: launch_tmean<FA_DTYPE_F16>(k, trim, grid, st, ds, nseg, dp); break;
+                        default: launch_tmean<FA_DTYPE_F64>(k, trim, grid, st, ds, nseg, dp); break;
+                      }
+                    });
 }
 
 }  // namespace
@@ -327,15 +266,16 @@ extern "C" {
 
 int fa_coord_trimmed_mean(fa_ctx* ctx, int dtype, int32_t num_segments, const int64_t* seg_numel, int32_t k,
                           int32_t trim, const void* const* d_in, void* const* d_out, void* hip_stream) {
-  return tmean_impl("fa_coord_trimmed_mean", ctx, dtype, num_segments, seg_numel, k, trim, d_in, 0, d_out, hip_stream);
+  return tmean_impl({"fa_coord_trimmed_mean", ctx, dtype, num_segments, seg_numel, k, d_in, 0, d_out, hip_stream}, trim);
 }
 
 int fa_coord_trimmed_mean_tiled(fa_ctx* ctx, int dtype, int32_t num_segments, const int64_t* seg_numel, int32_t k,
                                 int32_t trim, const void* const* d_in, int64_t tile_stride, void* const* d_out,
                                 void* hip_stream) {
   if (ctx && tile_stride <= 0) return fail(FA_ERR_INVALID, "fa_coord_trimmed_mean_tiled: tile_stride must be > 0");
-  return tmean_impl("fa_coord_trimmed_mean_tiled", ctx, dtype, num_segments, seg_numel, k, trim, d_in, tile_stride, d_out,
-                    hip_stream);
+  return tmean_impl({"fa_coord_trimmed_mean_tiled", ctx, dtype, num_segments, seg_numel, k, d_in, tile_stride, d_out,
+                     hip_stream},
+                    trim);
 }
 
 }  // extern "C"

@@ -856,59 +856,7 @@ class AggEngine:
         N.check(rc, "fa_mt_randint_sum")
         return out
 
-    def coord_median(self, segments: Sequence[Sequence[torch.Tensor]],
-                     outs: Optional[Sequence[torch.Tensor]] = None, stream=None) -> List[torch.Tensor]:
-        """Coordinate-wise median over clients (fa_coord_median): segments[s][i] = client i's
-        tensor of segment s (one dtype: float32, bfloat16, float16, float64); one launch."""
-        k = len(segments[0]) if segments else 0
-        if k == 0:
-            raise ValueError("coord_median: no client tensors")
-        dt = segments[0][0].dtype
-        if dt not in (torch.float32, torch.bfloat16, torch.float16, torch.float64):
-            raise TypeError(f"coord_median: unsupported dtype {dt}")
-        in_ptrs, numels, results = [], [], []
-        for s, seg in enumerate(segments):
-            if len(seg) != k:
-                raise ValueError(f"segment {s}: {len(seg)} clients, expected {k}")
-            for i, t in enumerate(seg):
-                if t.dtype != dt or t.shape != seg[0].shape:
-                    raise ValueError(f"segment {s} client {i}: dtype/shape mismatch")
-                _require_device(t, self.device, f"segment {s} client {i}")
-                in_ptrs.append(t.data_ptr())
-            if outs is not None:
-                o = outs[s]
-                if o.dtype != dt or o.numel() != seg[0].numel():
-                    raise ValueError(f"segment {s}: output must be {dt} with {seg[0].numel()} elements")
-                _require_device(o, self.device, f"segment {s} output")
-            else:
-                o = torch.empty(seg[0].shape, dtype=dt, device=self.device)
-            results.append(o)
-            numels.append(seg[0].numel())
-        rc = self._lib.fa_coord_median(self._ctx, DTYPE_CODE[dt], len(segments), N.i64_array(numels), k,
-                                       N.ptr_array(in_ptrs), N.ptr_array([o.data_ptr() for o in results]),
-                                       self._stream(stream))
-        N.check(rc, "fa_coord_median")
-        return results
-
-    def coord_median_tiled(self, buf: torch.Tensor, rows: Sequence[int], n: Optional[int] = None,
-                           out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
-        """Coordinate-wise median over rows of a TILE-INTERLEAVED arena group ``buf`` [tiles, capacity,
-        E] (fa_coord_median_tiled): the same selection, bit for bit, as ``coord_median`` over the
-        logical rows, read in the layout whose K tiles of a workgroup are one contiguous run."""
-        if buf.dtype not in (torch.float32, torch.bfloat16, torch.float16, torch.float64):
-            raise TypeError(f"coord_median_tiled: unsupported dtype {buf.dtype}")
-        n, ptrs, stride = self._tiled_args(buf, rows, 0, n, "coord_median_tiled")
-        if out is None:
-            out = torch.empty(n, dtype=buf.dtype, device=self.device)
-        elif out.dtype != buf.dtype or out.numel() != n or not out.is_contiguous():
-            raise ValueError(f"coord_median_tiled: output must be a contiguous {buf.dtype} tensor of {n} elements")
-        _require_device(out, self.device, "output")
-        if n == 0:
-            return out
-        rc = self._lib.fa_coord_median_tiled(self._ctx, DTYPE_CODE[buf.dtype], 1, N.i64_array([n]), len(rows), ptrs,
-                                             stride, N.ptr_array([out.data_ptr()]), self._stream(stream))
-        N.check(rc, "fa_coord_median_tiled")
-        return out
+    _COLUMN_DTYPES = (torch.float32, torch.bfloat16, torch.float16, torch.float64)
 
     @staticmethod
     def _check_trim(trim, k: int, what: str) -> int:
@@ -916,19 +864,16 @@ class AggEngine:
             raise ValueError(f"{what}: trim must be an integer with 0 <= trim and 2 * trim < K (trim {trim}, K {k})")
         return int(trim)
 
-    def coord_trimmed_mean(self, segments: Sequence[Sequence[torch.Tensor]], trim: int,
-                           outs: Optional[Sequence[torch.Tensor]] = None, stream=None) -> List[torch.Tensor]:
-        """Coordinate-wise trimmed mean over clients (fa_coord_trimmed_mean; Yin et al. 2018): per
-        coordinate the K values sorted (NaN largest), the ``trim`` smallest and largest dropped, the
-        rest summed in rank order in float64 from the first kept value, divided by K - 2 trim and
-        rounded to the dtype (include/fedagg_robust.h).  Arguments and results as ``coord_median``."""
+    def _column_op(self, what: str, segments, outs, stream, *trim) -> List[torch.Tensor]:
+        """The flat per-column operators (``what`` = coord_median, or coord_trimmed_mean followed by
+        its ``trim``): validates the segments, builds pointers, sizes and outputs, one launch of fa_<what>."""
         k = len(segments[0]) if segments else 0
         if k == 0:
-            raise ValueError("coord_trimmed_mean: no client tensors")
+            raise ValueError(f"{what}: no client tensors")
         dt = segments[0][0].dtype
-        if dt not in (torch.float32, torch.bfloat16, torch.float16, torch.float64):
-            raise TypeError(f"coord_trimmed_mean: unsupported dtype {dt}")
-        trim = self._check_trim(trim, k, "coord_trimmed_mean")
+        if dt not in self._COLUMN_DTYPES:
+            raise TypeError(f"{what}: unsupported dtype {dt}")
+        trim = [self._check_trim(b, k, what) for b in trim]
         in_ptrs, numels, results = [], [], []
         for s, seg in enumerate(segments):
             if len(seg) != k:
@@ -947,33 +892,58 @@ class AggEngine:
                 o = torch.empty(seg[0].shape, dtype=dt, device=self.device)
             results.append(o)
             numels.append(seg[0].numel())
-        rc = self._lib.fa_coord_trimmed_mean(self._ctx, DTYPE_CODE[dt], len(segments), N.i64_array(numels), k, trim,
-                                             N.ptr_array(in_ptrs), N.ptr_array([o.data_ptr() for o in results]),
-                                             self._stream(stream))
-        N.check(rc, "fa_coord_trimmed_mean")
+        rc = getattr(self._lib, "fa_" + what)(self._ctx, DTYPE_CODE[dt], len(segments), N.i64_array(numels), k, *trim,
+                                              N.ptr_array(in_ptrs), N.ptr_array([o.data_ptr() for o in results]),
+                                              self._stream(stream))
+        N.check(rc, "fa_" + what)
         return results
+
+    def _column_op_tiled(self, what: str, buf: torch.Tensor, rows, n, out, stream, *trim) -> torch.Tensor:
+        """The tiled per-column operators (``what`` = coord_median_tiled, or coord_trimmed_mean_tiled
+        followed by its ``trim``) over rows of a tile-interleaved arena group: one launch of fa_<what>."""
+        if buf.dtype not in self._COLUMN_DTYPES:
+            raise TypeError(f"{what}: unsupported dtype {buf.dtype}")
+        trim = [self._check_trim(b, len(rows), what) for b in trim]
+        n, ptrs, stride = self._tiled_args(buf, rows, 0, n, what)
+        if out is None:
+            out = torch.empty(n, dtype=buf.dtype, device=self.device)
+        elif out.dtype != buf.dtype or out.numel() != n or not out.is_contiguous():
+            raise ValueError(f"{what}: output must be a contiguous {buf.dtype} tensor of {n} elements")
+        _require_device(out, self.device, "output")
+        if n == 0:
+            return out
+        rc = getattr(self._lib, "fa_" + what)(self._ctx, DTYPE_CODE[buf.dtype], 1, N.i64_array([n]), len(rows), *trim,
+                                              ptrs, stride, N.ptr_array([out.data_ptr()]), self._stream(stream))
+        N.check(rc, "fa_" + what)
+        return out
+
+    def coord_median(self, segments: Sequence[Sequence[torch.Tensor]],
+                     outs: Optional[Sequence[torch.Tensor]] = None, stream=None) -> List[torch.Tensor]:
+        """Coordinate-wise median over clients (fa_coord_median): segments[s][i] = client i's
+        tensor of segment s (one dtype: float32, bfloat16, float16, float64); one launch."""
+        return self._column_op("coord_median", segments, outs, stream)
+
+    def coord_median_tiled(self, buf: torch.Tensor, rows: Sequence[int], n: Optional[int] = None,
+                           out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+        """Coordinate-wise median over rows of a TILE-INTERLEAVED arena group ``buf`` [tiles, capacity,
+        E] (fa_coord_median_tiled): the same selection, bit for bit, as ``coord_median`` over the
+        logical rows, read in the layout whose K tiles of a workgroup are one contiguous run."""
+        return self._column_op_tiled("coord_median_tiled", buf, rows, n, out, stream)
+
+    def coord_trimmed_mean(self, segments: Sequence[Sequence[torch.Tensor]], trim: int,
+                           outs: Optional[Sequence[torch.Tensor]] = None, stream=None) -> List[torch.Tensor]:
+        """Coordinate-wise trimmed mean over clients (fa_coord_trimmed_mean; Yin et al. 2018): per
+        coordinate the K values sorted (NaN largest), the ``trim`` smallest and largest dropped, the
+        rest summed in rank order in float64 from the first kept value, divided by K - 2 trim and
+        rounded to the dtype (include/fedagg_robust.h).  Arguments and results as ``coord_median``."""
+        return self._column_op("coord_trimmed_mean", segments, outs, stream, trim)
 
     def coord_trimmed_mean_tiled(self, buf: torch.Tensor, rows: Sequence[int], trim: int, n: Optional[int] = None,
                                  out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
         """Coordinate-wise trimmed mean over rows of a TILE-INTERLEAVED arena group ``buf`` [tiles,
         capacity, E] (fa_coord_trimmed_mean_tiled): bit for bit ``coord_trimmed_mean`` over the
         logical rows.  Arguments and results as ``coord_median_tiled``."""
-        if buf.dtype not in (torch.float32, torch.bfloat16, torch.float16, torch.float64):
-            raise TypeError(f"coord_trimmed_mean_tiled: unsupported dtype {buf.dtype}")
-        trim = self._check_trim(trim, len(rows), "coord_trimmed_mean_tiled")
-        n, ptrs, stride = self._tiled_args(buf, rows, 0, n, "coord_trimmed_mean_tiled")
-        if out is None:
-            out = torch.empty(n, dtype=buf.dtype, device=self.device)
-        elif out.dtype != buf.dtype or out.numel() != n or not out.is_contiguous():
-            raise ValueError(f"coord_trimmed_mean_tiled: output must be a contiguous {buf.dtype} tensor of {n} elements")
-        _require_device(out, self.device, "output")
-        if n == 0:
-            return out
-        rc = self._lib.fa_coord_trimmed_mean_tiled(self._ctx, DTYPE_CODE[buf.dtype], 1, N.i64_array([n]), len(rows),
-                                                   trim, ptrs, stride, N.ptr_array([out.data_ptr()]),
-                                                   self._stream(stream))
-        N.check(rc, "fa_coord_trimmed_mean_tiled")
-        return out
+        return self._column_op_tiled("coord_trimmed_mean_tiled", buf, rows, n, out, stream, trim)
 
     MAX_PAIR_K = 128  # kMaxPairK (fedml_amd/csrc/robust.hip): clients per fa_pairwise_sqdist launch
 

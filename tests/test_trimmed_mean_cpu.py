@@ -21,6 +21,13 @@ def test_null_ctx_returns_invalid():
     assert rc == N.FA_ERR_INVALID and b"ctx" in L.fa_last_error()
     rc = L.fa_coord_trimmed_mean_tiled(None, N.F32, 1, None, 4, 1, None, 0, None, None)
     assert rc == N.FA_ERR_INVALID and b"ctx" in L.fa_last_error()
+    # the median's entries share the driver: the context is checked before tile_stride there too
+    rc = L.fa_coord_median(None, N.F32, 1, None, 4, None, None, None)
+    assert rc == N.FA_ERR_INVALID and b"ctx" in L.fa_last_error()
+    rc = L.fa_coord_median_tiled(None, N.F32, 1, None, 4, None, 4096, None, None)
+    assert rc == N.FA_ERR_INVALID and b"ctx" in L.fa_last_error()
+    rc = L.fa_coord_median_tiled(None, N.F32, 1, None, 4, None, 0, None, None)
+    assert rc == N.FA_ERR_INVALID and b"ctx" in L.fa_last_error()
 
 
 def test_symbols_are_declared_and_exported():

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Generates fedml_amd/csrc/median_nets.h: straight-line selection networks for the coordinate-wise
-median kernel (robust.hip).
+median kernel (median.hip).
 
 For every bucket size B in 8, 16, ..., 128: Batcher's odd-even merge sort of P2 = next power of two
 >= B keys, where the P2 - B extra inputs are compile-time sentinels -- Lc low (below every key)
@@ -8,7 +8,7 @@ and Hc high, Lc chosen so that the lower median of the B keys, rank (B-1)//2, is
 all P2.  A comparator with a constant input is a renaming (no instruction); the rest are kept in
 SSA form and pruned backwards to what the output at rank P2/2 - 1 depends on (a comparator whose
 min or max half is dead emits only the other half).  The kernel pads K real keys to B with
-runtime low/high sentinels in the same way (robust.hip), so one network serves K in (B-8, B].
+runtime low/high sentinels in the same way (median.hip), so one network serves K in (B-8, B].
 
 Also SortNet<N> (N = 36, 40, ..., 64: a sort of N keys) for the two-lanes-per-column kernel k_median_2l.
 
@@ -164,7 +164,7 @@ def main(path):
         body.append(f"// B = {B}: {ops} min/max ops\n" + code)
     body.append("template <int B, typename K> __device__ __forceinline__ K select_mid(const K (&x)[B]) {\n"
                 "  return MidNet<B>::run(x);\n}")
-    # k_median_2l / k_median_4l (robust.hip): a column's B keys split over two (four) lanes, N = B/2
+    # k_median_2l / k_median_4l (median.hip): a column's B keys split over two (four) lanes, N = B/2
     # (B/4) keys each; every lane sorts its N keys in place (all N outputs are used by the merge).
     # Network: odd-even merge sort of the next power of two >= N with the extra inputs compile-time
     # high sentinels folded away (a comparator with a constant input is a renaming).
@@ -210,7 +210,7 @@ def main(path):
            "// sentinels folded away.  Keys: uint32 or\n" if BASE16 else
            "// network of the next power of two with compile-time sentinels folded away.  Keys: uint32 or\n") +
         "// float (one coordinate per lane) or two uint16 keys packed in 32 bits (two coordinates per lane,\n"
-        "// v_pk_min_u16 / v_pk_max_u16).  Used by the k_median kernels (robust.hip).\n"
+        "// v_pk_min_u16 / v_pk_max_u16).  Used by the k_median kernels (median.hip).\n"
         "#pragma once\n\n"
         "typedef unsigned short fa_u16x2 __attribute__((ext_vector_type(2)));\n"
         "__device__ __forceinline__ unsigned kmin(unsigned a, unsigned b) { return min(a, b); }\n"
