@@ -39,6 +39,7 @@ import torch
 
 from . import _host
 from .engine import MUL_N_DIV_N, MUL_W, SUM, AggEngine, get_engine, out_dtype
+from .weiszfeld import weiszfeld_driver
 
 _ALIGN_ELEMS = 64
 _SUPPORTED = (torch.float32, torch.bfloat16, torch.float16, torch.float64, torch.int64)
@@ -106,6 +107,17 @@ _ADOPTED: Dict[int, Tuple["weakref.ref", int]] = {}
 # c10::ScalarType codes (match_rows compares them with the values' scalar_type())
 _SCALAR_TYPE = {torch.uint8: 0, torch.int8: 1, torch.int16: 2, torch.int32: 3, torch.int64: 4, torch.float16: 5,
                 torch.float32: 6, torch.float64: 7, torch.bool: 11, torch.bfloat16: 15}
+
+
+def sum_stats(stats: Sequence[torch.Tensor]) -> Tuple[List[float], List[float]]:
+    """(d2, ss) host floats of one geometric-median pass from its [2, K] device tensors, one per
+    dtype group: one copy to the host, the groups added there in the order given."""
+    h = (stats[0] if len(stats) == 1 else torch.stack(list(stats))).cpu().reshape(len(stats), 2, -1).tolist()
+    d2, ss = h[0]
+    for g in h[1:]:
+        d2 = [a + b for a, b in zip(d2, g[0])]
+        ss = [a + b for a, b in zip(ss, g[1])]
+    return d2, ss
 
 
 def tile_elems(dt: torch.dtype) -> int:
@@ -517,6 +529,48 @@ class ClientArena:
         per dtype group: tiled arenas through fa_coord_trimmed_mean_tiled, client-major arenas over the
         row views.  Float groups only.  Returns per-key views."""
         return self._column_op("trimmed_mean", clients, ValueError("trimmed_mean: no client rows"), out, trim)
+
+    def geometric_median(self, counts: Sequence[float], iters: int = 3, nu: float = 1e-6,
+                         clients: Optional[Sequence[int]] = None,
+                         out: Optional[Dict[torch.dtype, torch.Tensor]] = None,
+                         info: Optional[dict] = None) -> "OrderedDict[str, torch.Tensor]":
+        """Geometric median of the given client rows (default: all) weighted by ``counts`` (aligned
+        with ``clients``), by ``iters`` smoothed Weiszfeld iterations after the weighted mean
+        (fedml_amd/weiszfeld.py): ``iters`` + 1 passes, each ONE fa_weighted_sum_sqdist launch per dtype
+        group (tiled arenas through the tiled entry, client-major arenas over the row views) and one
+        copy of 2K doubles to the host; with several dtype groups the distances are added across
+        groups on the host in the order of ``self.bufs``.  Rows holding a NaN or Inf are dropped
+        (``info["dropped"]``, positions in ``clients``).  Float groups only.  ``info`` (optional dict)
+        receives the driver's traces.  Returns per-key views of the last pass's weighted sum."""
+        rows = list(range(self.capacity)) if clients is None else list(clients)
+        if not rows:
+            raise ValueError("geometric_median: no client rows")
+        if len(counts) != len(rows):
+            raise ValueError("geometric_median: need one count per client row")
+        if any(dt not in (torch.float32, torch.bfloat16, torch.float16, torch.float64) for dt in self.bufs):
+            raise TypeError("geometric_median: the arena holds a non-float dtype group")
+        self._wait_ingest()
+        outs: Dict[torch.dtype, torch.Tensor] = {}
+        for dt, buf in self.bufs.items():
+            o = out[dt] if out is not None else None
+            outs[dt] = o if o is not None else torch.empty(self.layout.group_numel[dt], dtype=dt, device=buf.device)
+
+        def step(coef, idx):
+            sel = [rows[j] for j in idx]
+            stats = []
+            for dt, buf in self.bufs.items():
+                n = self.layout.group_numel[dt]
+                if self.tiled:
+                    stats.append(self.engine.weighted_sum_sqdist_tiled(buf, sel, coef, n=n, out=outs[dt])[1])
+                else:
+                    stats.append(self.engine.weighted_sum_sqdist([[buf[i][:n] for i in sel]], coef,
+                                                                 outs=[outs[dt]])[1])
+            return sum_stats(stats)
+
+        res = weiszfeld_driver(counts, iters, nu, step)
+        if info is not None:
+            info.update(res)
+        return self.layout.carve(outs)
 
     def _pair_groups(self) -> Optional[torch.dtype]:
         """The float dtype when the arena holds exactly one float group and one int64 group."""

@@ -70,7 +70,7 @@ class ServerAggregator(ABC):
         return raw_client_model_or_grad_list, client_idxs
 
     def aggregate(self, raw_client_model_or_grad_list: List[Tuple[float, OrderedDict]]):
-        """Reference :67-76 -> the on-aggregation defense (wise_median, coordinate_trimmed_mean) or
+        """Reference :67-76 -> the on-aggregation defense (wise_median, coordinate_trimmed_mean, geometric_median) or
         FedMLAggOperator.agg."""
         d = FedMLDefender.get_instance()
         if d.is_defense_enabled():

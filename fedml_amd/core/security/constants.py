@@ -4,3 +4,4 @@ DEFENSE_MULTIKRUM = "multikrum"
 DEFENSE_TRIMMED_MEAN = "trimmed_mean"
 DEFENSE_WISE_MEDIAN = "wise_median"
 DEFENSE_COORD_TRIMMED_MEAN = "coordinate_trimmed_mean"  # no reference name: the per-coordinate trimmed mean (Yin et al. 2018)
+DEFENSE_GEOMETRIC_MEDIAN = "geometric_median"  # no reference name here (its RFA stays unserved): smoothed Weiszfeld, contract in fedagg_robust.h

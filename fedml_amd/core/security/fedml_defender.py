@@ -1,10 +1,13 @@
 """FedMLDefender singleton (reference: python/fedml/core/security/fedml_defender.py:40-196) for the
-robust aggregators of this engine: krum / multikrum, trimmed_mean, wise_median and
+robust aggregators of this engine: krum / multikrum, trimmed_mean, wise_median,
 coordinate_trimmed_mean (the per-coordinate trimmed mean of Yin et al. 2018, which the reference
-lacks: its trimmed_mean trims whole clients and keeps that meaning here).  Same dispatch
+lacks: its trimmed_mean trims whole clients and keeps that meaning here) and geometric_median (the
+sample-weighted geometric median by the smoothed Weiszfeld iteration of Pillutla et al.; config
+geomed_iters, geomed_nu; the reference's own RFA name stays unserved).  Same dispatch
 (which defenses act before / on / after aggregation) and the same entry points; the per-element work
-runs in the HIP kernels (fedml_amd/csrc/median.hip, trimmed.hip, robust.hip).  Other defense types of
-the reference are outside the aggregation path and raise NotImplementedError when configured.
+runs in the HIP kernels (fedml_amd/csrc/median.hip, trimmed.hip, wsum_dist.hip, robust.hip).  Other
+defense types of the reference are outside the aggregation path and raise NotImplementedError when
+configured.
 """
 from __future__ import annotations
 
@@ -12,11 +15,12 @@ import logging
 from collections import OrderedDict
 from typing import Any, Callable, List, Tuple
 
-from .constants import (DEFENSE_COORD_TRIMMED_MEAN, DEFENSE_KRUM, DEFENSE_MULTIKRUM, DEFENSE_TRIMMED_MEAN,
-                        DEFENSE_WISE_MEDIAN)
+from .constants import (DEFENSE_COORD_TRIMMED_MEAN, DEFENSE_GEOMETRIC_MEDIAN, DEFENSE_KRUM, DEFENSE_MULTIKRUM,
+                        DEFENSE_TRIMMED_MEAN, DEFENSE_WISE_MEDIAN)
 from .defense.coordinate_trimmed_mean_defense import CoordinateTrimmedMeanDefense
 from .defense.coordinate_wise_median_defense import CoordinateWiseMedianDefense
 from .defense.coordinate_wise_trimmed_mean_defense import CoordinateWiseTrimmedMeanDefense
+from .defense.geometric_median_defense import GeometricMedianDefense
 from .defense.krum_defense import KrumDefense
 
 
@@ -48,10 +52,13 @@ class FedMLDefender:
                 self.defender = CoordinateWiseTrimmedMeanDefense(args)
             elif self.defense_type == DEFENSE_COORD_TRIMMED_MEAN:
                 self.defender = CoordinateTrimmedMeanDefense(args)
+            elif self.defense_type == DEFENSE_GEOMETRIC_MEDIAN:
+                self.defender = GeometricMedianDefense(args)
             else:
                 raise NotImplementedError(
                     f"defense_type {self.defense_type!r} is not served by the MI355X engine "
-                    f"(supported: krum, multikrum, trimmed_mean, wise_median, coordinate_trimmed_mean)")
+                    f"(supported: krum, multikrum, trimmed_mean, wise_median, coordinate_trimmed_mean, "
+                    f"geometric_median)")
         else:
             self.is_enabled = False
             self.defense_type = None
@@ -62,7 +69,8 @@ class FedMLDefender:
 
     def is_defense_on_aggregation(self):
         return self.is_defense_enabled() and self.defense_type in [DEFENSE_WISE_MEDIAN,
-                                                                               DEFENSE_COORD_TRIMMED_MEAN]
+                                                                               DEFENSE_COORD_TRIMMED_MEAN,
+                                                                               DEFENSE_GEOMETRIC_MEDIAN]
 
     def is_defense_before_aggregation(self):
         return self.is_defense_enabled() and self.defense_type in [DEFENSE_KRUM, DEFENSE_MULTIKRUM,

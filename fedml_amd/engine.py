@@ -945,6 +945,83 @@ class AggEngine:
         logical rows.  Arguments and results as ``coord_median_tiled``."""
         return self._column_op_tiled("coord_trimmed_mean_tiled", buf, rows, n, out, stream, trim)
 
+    def _sqdist_coef(self, what: str, coef, k: int):
+        if coef is None or len(coef) != k:
+            raise ValueError(f"{what}: need one coefficient per client")
+        return N.f64_array(coef)
+
+    def weighted_sum_sqdist(self, segments: Sequence[Sequence[torch.Tensor]], coef: Sequence[float],
+                            outs: Optional[Sequence[torch.Tensor]] = None,
+                            stream=None) -> Tuple[List[torch.Tensor], torch.Tensor]:
+        """One smoothed Weiszfeld pass (fa_weighted_sum_sqdist): the MUL_W weighted sum of the clients
+        -- bit for bit ``weighted_sum_multi(segments, MUL_W, coef)`` -- and, from the same read of the
+        inputs, ``stats`` = a [2, K] float64 device tensor: stats[0, i] = sum over all segments of
+        (x_i - out)^2 against the stored out, stats[1, i] = sum of x_i^2 (include/fedagg_robust.h).
+        segments[s][i] = client i's tensor of segment s (one dtype: float32, bfloat16, float16,
+        float64); one launch.  Returns (outs, stats)."""
+        what = "weighted_sum_sqdist"
+        k = len(segments[0]) if segments else 0
+        if k == 0:
+            raise ValueError(f"{what}: no client tensors")
+        dt = segments[0][0].dtype
+        if dt not in self._COLUMN_DTYPES:
+            raise TypeError(f"{what}: unsupported dtype {dt}")
+        c = self._sqdist_coef(what, coef, k)
+        in_ptrs, numels, results = [], [], []
+        for s, seg in enumerate(segments):
+            if len(seg) != k:
+                raise ValueError(f"segment {s}: {len(seg)} clients, expected {k}")
+            for i, t in enumerate(seg):
+                if t.dtype != dt or t.shape != seg[0].shape:
+                    raise ValueError(f"segment {s} client {i}: dtype/shape mismatch")
+                _require_device(t, self.device, f"segment {s} client {i}")
+                in_ptrs.append(t.data_ptr())
+            if outs is not None:
+                o = outs[s]
+                if o.dtype != dt or o.numel() != seg[0].numel():
+                    raise ValueError(f"segment {s}: output must be {dt} with {seg[0].numel()} elements")
+                _require_device(o, self.device, f"segment {s} output")
+            else:
+                o = torch.empty(seg[0].shape, dtype=dt, device=self.device)
+            results.append(o)
+            numels.append(seg[0].numel())
+        nm = N.i64_array(numels)
+        need = int(self._lib.fa_weighted_sum_sqdist_scratch_bytes(len(segments), nm, k))
+        scratch = self._scratch("wsum_sqdist", need, stream)
+        stats = torch.empty((2, k), dtype=torch.float64, device=self.device)
+        rc = self._lib.fa_weighted_sum_sqdist(self._ctx, DTYPE_CODE[dt], len(segments), nm, k, N.ptr_array(in_ptrs), c,
+                                              N.ptr_array([o.data_ptr() for o in results]), stats.data_ptr(),
+                                              scratch.data_ptr(), need, self._stream(stream))
+        N.check(rc, "fa_weighted_sum_sqdist")
+        return results, stats
+
+    def weighted_sum_sqdist_tiled(self, buf: torch.Tensor, rows: Sequence[int], coef: Sequence[float],
+                                  n: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                                  stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``weighted_sum_sqdist`` over rows of a TILE-INTERLEAVED arena group ``buf`` [tiles, capacity,
+        E] (fa_weighted_sum_sqdist_tiled): the same out, bit for bit, as over the logical rows.
+        Returns (out, stats); out is flat, ``n`` elements (default: all)."""
+        what = "weighted_sum_sqdist_tiled"
+        if buf.dtype not in self._COLUMN_DTYPES:
+            raise TypeError(f"{what}: unsupported dtype {buf.dtype}")
+        n, ptrs, stride = self._tiled_args(buf, rows, 0, n, what)
+        k = len(rows)
+        c = self._sqdist_coef(what, coef, k)
+        if out is None:
+            out = torch.empty(n, dtype=buf.dtype, device=self.device)
+        elif out.dtype != buf.dtype or out.numel() != n or not out.is_contiguous():
+            raise ValueError(f"{what}: output must be a contiguous {buf.dtype} tensor of {n} elements")
+        _require_device(out, self.device, "output")
+        nm = N.i64_array([n])
+        need = int(self._lib.fa_weighted_sum_sqdist_scratch_bytes(1, nm, k))
+        scratch = self._scratch("wsum_sqdist", need, stream)
+        stats = torch.empty((2, k), dtype=torch.float64, device=self.device)
+        rc = self._lib.fa_weighted_sum_sqdist_tiled(self._ctx, DTYPE_CODE[buf.dtype], 1, nm, k, ptrs, stride, c,
+                                                    N.ptr_array([out.data_ptr()]), stats.data_ptr(),
+                                                    scratch.data_ptr(), need, self._stream(stream))
+        N.check(rc, "fa_weighted_sum_sqdist_tiled")
+        return out, stats
+
     MAX_PAIR_K = 128  # kMaxPairK (fedml_amd/csrc/robust.hip): clients per fa_pairwise_sqdist launch
 
     def pairwise_sqdist(self, segments: Sequence[Sequence[torch.Tensor]], stream=None,

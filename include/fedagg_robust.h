@@ -8,6 +8,9 @@
  *   fa_coord_median_tiled  the same over tile-interleaved arena rows
  *   fa_coord_trimmed_mean, fa_coord_trimmed_mean_tiled  no reference code: the per-coordinate trimmed
  *                       mean of Yin et al. 2018 (the reference's "trimmed mean" trims whole clients)
+ *   fa_weighted_sum_sqdist, fa_weighted_sum_sqdist_tiled  no reference code here: one smoothed Weiszfeld
+ *                       pass of the geometric median (RFA), the weighted sum fused with every
+ *                       client's squared distance to it
  *   fa_pairwise_sqdist  core/security/defense/krum_defense.py:52-66 (_compute_krum_score's
  *                       compute_euclidean_distance(v_i, v_j) ** 2 for every pair)
  *   fa_pairwise_sqdist_rt  the same for bfloat16 / float16 models (differences in the model dtype)
@@ -77,6 +80,41 @@ int fa_coord_trimmed_mean(fa_ctx *ctx, int dtype, int32_t num_segments, const in
 int fa_coord_trimmed_mean_tiled(fa_ctx *ctx, int dtype, int32_t num_segments, const int64_t *seg_numel,
                                 int32_t k, int32_t trim, const void *const *d_in, int64_t tile_stride,
                                 void *const *d_out, void *hip_stream);
+
+/*
+ * One pass of the smoothed Weiszfeld iteration for the geometric median (Pillutla, Kakade, Harchaoui,
+ * "Robust Aggregation for Federated Learning"): the weighted sum of the k clients AND every client's
+ * squared distance to it, in one read of the inputs from HBM.  Pointer layout d_in[s * k + i], dtypes
+ * (F32, BF16, F16, F64; I64: FA_ERR_DTYPE), segment rules, host tables staged by the library,
+ * validation before any HIP call (the context first), asynchrony on the caller's stream: fa_coord_median's.
+ * Any k >= 1.  coef: k host doubles (required).  Contract, for every element e of every segment:
+ *   out[e] = fa_weighted_sum's FA_MODE_MUL_W result for the same inputs and coef, bit for bit (NaNs
+ *            included): clients in order, t_i = op(x_i * c_i), out = t_0, out = op(out + t_i), op
+ *            rounding once to the storage type, nothing fused, coef cast to the op type;
+ *   d_stats = 2 k float64 on the device, all written by the call:
+ *     d_stats[i]     = d2_i = sum_e (x_i[e] - out[e])^2 over all segments, against the STORED
+ *                      (rounded) out[e];
+ *     d_stats[k + i] = ss_i = sum_e x_i[e]^2.
+ * The differences are formed in float32 from exactly widened inputs (float64 for F64), squared and
+ * summed in float64; the order of the sums is the implementation's, and fixed: the same call gives
+ * the same 2 k bit patterns every time (no floating-point atomics).  All inputs finite: each sum is
+ * within 1e-6 relative of its exact value (tests/test_gpu_geometric_median.py; one float32 rounding
+ * of a difference costs at most 2^-23 on its square, the terms are non-negative), and an exact value
+ * of 0 gives exactly 0 (k = 1, coef 1: out = x, d2 = 0).  ss_i is non-finite exactly when client i
+ * holds a NaN or +-Inf (F64: also when a square overflows); d2_i is non-finite when any of its terms is.
+ * d_scratch: device buffer of at least fa_weighted_sum_sqdist_scratch_bytes(...) bytes (per-workgroup
+ * partial sums; caller-owned, reusable; the size serves every dtype; 0 for invalid arguments).
+ */
+int fa_weighted_sum_sqdist(fa_ctx *ctx, int dtype, int32_t num_segments, const int64_t *seg_numel, int32_t k,
+                           const void *const *d_in, const double *coef, void *const *d_out, void *d_stats,
+                           void *d_scratch, size_t scratch_bytes, void *hip_stream);
+/* The same over tile-interleaved client rows (addressing and tile rules of fa_coord_median_tiled):
+ * out bit for bit fa_weighted_sum_sqdist's over the logical rows, the sums within the same bound. */
+int fa_weighted_sum_sqdist_tiled(fa_ctx *ctx, int dtype, int32_t num_segments, const int64_t *seg_numel, int32_t k,
+                                 const void *const *d_in, int64_t tile_stride, const double *coef,
+                                 void *const *d_out, void *d_stats, void *d_scratch, size_t scratch_bytes,
+                                 void *hip_stream);
+size_t fa_weighted_sum_sqdist_scratch_bytes(int32_t num_segments, const int64_t *seg_numel, int32_t k);
 
 /*
  * Pairwise squared Euclidean distances of k float32 client vectors (2 <= k <= 128), each given
