@@ -22,13 +22,9 @@ import math
 from collections import OrderedDict
 from typing import Any, Callable, List, Tuple
 
-import torch
-
-from ....arena import resident_rows, sum_stats
-from ....engine import get_engine
+from ....arena import sum_stats
 from ....weiszfeld import weiszfeld_driver
-
-_NATIVE = (torch.float32, torch.bfloat16, torch.float16, torch.float64)
+from ._float_keys import defend_float_keys
 
 
 class GeometricMedianDefense(object):
@@ -49,64 +45,22 @@ class GeometricMedianDefense(object):
 
     def defend_on_aggregation(self, raw_client_grad_list: List[Tuple[float, OrderedDict]],
                               base_aggregation_func: Callable = None, extra_auxiliary_info: Any = None):
-        grads = [g for _, g in raw_client_grad_list]
-        if len(grads) == 0:
+        if len(raw_client_grad_list) == 0:
             raise ValueError("geometric_median: no client updates")
         counts = [float(n) for n, _ in raw_client_grad_list]
-        first = grads[0]
-        fkeys = [k for k, v in first.items() if v.dtype in _NATIVE]
-        okeys = [k for k in first if k not in set(fkeys)]
-        if okeys and base_aggregation_func is None:
-            raise TypeError(f"geometric_median: keys {okeys} are not floating point and no base aggregation "
-                            f"function was given for them")
-        result = {}
-        hit = resident_rows(grads) if fkeys and not okeys else None
-        if hit is not None and all(dt in _NATIVE for dt in hit[0].bufs):
-            # updates adopted into ONE arena's rows, float groups only: the passes run over the rows
-            arena, rows = hit
-            info = {}
-            result.update(arena.geometric_median(counts, self.iters, self.nu, rows, info=info))
-            self.last_info = info
-        elif fkeys:
-            dev = next((g[k].device for g in grads for k in fkeys if g[k].is_cuda), None)
-            eng = get_engine(dev.index if dev is not None else None)
-            groups = OrderedDict()  # dtype -> keys
-            for k in fkeys:
-                groups.setdefault(first[k].dtype, []).append(k)
-            work = []  # per dtype group: (segments [key][client], outs per key, the flat output)
-            for dt, keys in groups.items():
-                segs = []
-                for k in keys:
-                    col = []
-                    for g in grads:
-                        t = g[k]
-                        if t.dtype != dt or t.shape != first[k].shape:
-                            raise ValueError(f"geometric_median: key {k!r} differs in dtype or shape between clients")
-                        col.append(t.to(eng.device).contiguous().reshape(-1))
-                    segs.append(col)
-                vec = torch.empty(sum(c[0].numel() for c in segs), dtype=dt, device=eng.device)
-                outs, pos = [], 0
-                for c in segs:
-                    outs.append(vec[pos:pos + c[0].numel()])
-                    pos += c[0].numel()
-                work.append((segs, outs, vec))
 
+        def on_arena(arena, rows):  # the passes run over the rows
+            info = {}
+            res = arena.geometric_median(counts, self.iters, self.nu, rows, info=info)
+            self.last_info = info
+            return res
+
+        def on_engine(eng, work):
             def step(coef, idx):
                 return sum_stats([eng.weighted_sum_sqdist([[col[i] for i in idx] for col in segs], coef, outs=outs)[1]
-                                  for segs, outs, _ in work])
+                                  for segs, outs in work])
 
             self.last_info = weiszfeld_driver(counts, self.iters, self.nu, step)
-            for (dt, keys), (_, _, vec) in zip(groups.items(), work):
-                if dev is None:
-                    vec = vec.cpu()  # CPU dicts in, CPU tensors out (the copy waits for the launches)
-                pos = 0
-                for k in keys:
-                    n = first[k].numel()
-                    result[k] = vec[pos:pos + n].view(first[k].shape)
-                    pos += n
-        if okeys:
-            base = base_aggregation_func(args=self.config, raw_grad_list=[
-                (n, OrderedDict((k, g[k]) for k in okeys)) for n, g in raw_client_grad_list])
-            for k in okeys:
-                result[k] = base[k].to(first[k].device)
-        return OrderedDict((k, result[k]) for k in first)
+
+        return defend_float_keys("geometric_median", self.config, raw_client_grad_list, base_aggregation_func,
+                                 on_arena, on_engine)

@@ -1,5 +1,6 @@
 // fa_internal.h -- pieces shared by the translation units of libfedagg.so (not part of the ABI):
-// the context with its pinned/device staging slots, error reporting, the segment table.
+// the context with its pinned/device staging slots, error reporting, the segment table.  The device
+// element arithmetic and conversions shared by the kernels are elem.h's.
 #pragma once
 
 #include <hip/hip_runtime.h>

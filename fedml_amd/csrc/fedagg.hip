@@ -37,6 +37,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "elem.h"
 #include "fa_internal.h"
 
 using namespace fa_detail;
@@ -56,123 +57,24 @@ struct MixRow {             // one output row of a mixing matrix
 static_assert(sizeof(MixRow) == 32, "MixRow layout");
 
 // --------------------------------------------------------------------------------------------
-// Exact per-op arithmetic.
-__device__ __forceinline__ float op_mul(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ float op_add(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ float op_div(float a, float b) { return __fdiv_rn(a, b); }
-__device__ __forceinline__ double op_mul(double a, double b) { return __dmul_rn(a, b); }
-__device__ __forceinline__ double op_add(double a, double b) { return __dadd_rn(a, b); }
-__device__ __forceinline__ double op_div(double a, double b) { return __ddiv_rn(a, b); }
-
-__device__ __forceinline__ float bf16_round(float x) { return (float)(__bf16)x; }
-__device__ __forceinline__ unsigned bf16_bits(float x) {
-  return (unsigned)__builtin_bit_cast(unsigned short, (__bf16)x);
-}
-// The f32 -> f16 rounding must see a MATERIALISED f32 value: otherwise the gfx950 backend folds
-// fptrunc(fmul(fpext(h), c)) into v_fma_mixlo_f16, which rounds the exact product to f16 ONCE,
-// while the reference (PyTorch CPU) rounds it to f32 first and then to f16 (double rounding).
-// The empty asm pins the f32 intermediate in a VGPR (no instruction is emitted).
-__device__ __forceinline__ float pin_f32(float x) {
-  asm("" : "+v"(x));
-  return x;
-}
-__device__ __forceinline__ float f16_round(float x) { return (float)(_Float16)pin_f32(x); }
-__device__ __forceinline__ unsigned f16_bits(float x) {
-  return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)pin_f32(x));
-}
-__device__ __forceinline__ float f16_from_bits(unsigned b) {
-  return (float)__builtin_bit_cast(_Float16, (unsigned short)b);
-}
-
-// --------------------------------------------------------------------------------------------
-// Element traits per (input dtype, mode):
+// Element traits per (input dtype, mode), on top of the shared arithmetic and conversions (elem.h):
 //   R     raw element value after unpacking (exact widening: float for f32/bf16/f16)
 //   A     accumulator / op type;  C coefficient type;  D divisor type
 //   V     elements per 16-byte input vector;  IN_BYTES / OUT_BYTES element sizes
 //   term  t_i of the contract;  acc   op(acc + t);  zero  the exact additive identity
-template <int DT, int MODE> struct Tr;
-
-template <int MODE> struct TrFloatBase {
-  using A = float; using C = float; using D = float; using R = float;
-  __device__ static C coef(double c) { return (float)c; }
-  __device__ static D div(double d) { return (float)d; }
-  __device__ static A zero() { return -0.0f; }
-};
-
-template <int MODE> struct Tr<FA_DTYPE_F32, MODE> : TrFloatBase<MODE> {
-  static constexpr int V = 4, IN_BYTES = 4, OUT_BYTES = 4;
-  __device__ static float rnd(float x) { return x; }
-  __device__ static void unpack(u32x4 r, float (&x)[V]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) x[j] = __uint_as_float(r[j]);
-  }
-  __device__ static float ld1(const void* p, int64_t e) { return ((const float*)p)[e]; }
-  __device__ static void st1(void* p, int64_t e, float v) { ((float*)p)[e] = v; }
-  __device__ static void stv(void* p, const float (&a)[V]) {
-    u32x4 w = {__float_as_uint(a[0]), __float_as_uint(a[1]), __float_as_uint(a[2]), __float_as_uint(a[3])};
-    __builtin_nontemporal_store(w, (__attribute__((address_space(1))) u32x4*)p);
-  }
-};
-
-template <int MODE> struct Tr<FA_DTYPE_BF16, MODE> : TrFloatBase<MODE> {
-  static constexpr int V = 8, IN_BYTES = 2, OUT_BYTES = 2;
-  __device__ static float rnd(float x) { return bf16_round(x); }
-  __device__ static void unpack(u32x4 r, float (&x)[V]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      x[2 * j] = __uint_as_float(r[j] << 16);
-      x[2 * j + 1] = __uint_as_float(r[j] & 0xFFFF0000u);
-    }
-  }
-  __device__ static float ld1(const void* p, int64_t e) {
-    return __uint_as_float((unsigned)((const unsigned short*)p)[e] << 16);
-  }
-  __device__ static void st1(void* p, int64_t e, float v) { ((unsigned short*)p)[e] = (unsigned short)bf16_bits(v); }
-  __device__ static void stv(void* p, const float (&a)[V]) {
-    u32x4 w;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) w[j] = bf16_bits(a[2 * j]) | (bf16_bits(a[2 * j + 1]) << 16);
-    __builtin_nontemporal_store(w, (__attribute__((address_space(1))) u32x4*)p);
-  }
-};
-
-template <int MODE> struct Tr<FA_DTYPE_F16, MODE> : TrFloatBase<MODE> {
-  static constexpr int V = 8, IN_BYTES = 2, OUT_BYTES = 2;
-  __device__ static float rnd(float x) { return f16_round(x); }
-  __device__ static void unpack(u32x4 r, float (&x)[V]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      x[2 * j] = f16_from_bits(r[j] & 0xFFFFu);
-      x[2 * j + 1] = f16_from_bits(r[j] >> 16);
-    }
-  }
-  __device__ static float ld1(const void* p, int64_t e) { return f16_from_bits(((const unsigned short*)p)[e]); }
-  __device__ static void st1(void* p, int64_t e, float v) { ((unsigned short*)p)[e] = (unsigned short)f16_bits(v); }
-  __device__ static void stv(void* p, const float (&a)[V]) {
-    u32x4 w;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) w[j] = f16_bits(a[2 * j]) | (f16_bits(a[2 * j + 1]) << 16);
-    __builtin_nontemporal_store(w, (__attribute__((address_space(1))) u32x4*)p);
-  }
-};
-
-template <int MODE> struct Tr<FA_DTYPE_F64, MODE> {
-  using A = double; using C = double; using D = double; using R = double;
-  static constexpr int V = 2, IN_BYTES = 8, OUT_BYTES = 8;
-  __device__ static C coef(double c) { return c; }
-  __device__ static D div(double d) { return d; }
-  __device__ static A zero() { return -0.0; }
-  __device__ static double rnd(double x) { return x; }
-  __device__ static void unpack(u32x4 r, double (&x)[V]) {
-    x[0] = __builtin_bit_cast(double, u32x2{r[0], r[1]});
-    x[1] = __builtin_bit_cast(double, u32x2{r[2], r[3]});
-  }
-  __device__ static double ld1(const void* p, int64_t e) { return ((const double*)p)[e]; }
-  __device__ static void st1(void* p, int64_t e, double v) { ((double*)p)[e] = v; }
-  __device__ static void stv(void* p, const double (&a)[V]) {
-    u32x2 lo = __builtin_bit_cast(u32x2, a[0]), hi = __builtin_bit_cast(u32x2, a[1]);
-    u32x4 w = {lo[0], lo[1], hi[0], hi[1]};
-    __builtin_nontemporal_store(w, (__attribute__((address_space(1))) u32x4*)p);
+// The loads are generic-pointer element loads, the vector store is non-temporal.
+template <int DT, int MODE> struct Tr : El<DT> {  // the float dtypes; int64 below
+  using E = El<DT>;
+  using A = typename E::A; using C = A; using D = A; using R = A;
+  using S = typename E::S;
+  static constexpr int V = E::V, IN_BYTES = E::SZ, OUT_BYTES = E::SZ;
+  __device__ static C coef(double c) { return (C)c; }
+  __device__ static D div(double d) { return (D)d; }
+  __device__ static A zero() { return (A)-0.0; }
+  __device__ static A ld1(const void* p, int64_t e) { return E::from_bits(((const S*)p)[e]); }
+  __device__ static void st1(void* p, int64_t e, A v) { ((S*)p)[e] = E::bits(v); }
+  __device__ static void stv(void* p, const A (&a)[V]) {
+    __builtin_nontemporal_store(E::pack(a), (__attribute__((address_space(1))) u32x4*)p);
   }
 };
 
@@ -185,10 +87,7 @@ template <int MODE> struct Tr<FA_DTYPE_I64, MODE> {
   __device__ static D div(double d) { return (float)d; }
   __device__ static A zero() { return -0.0f; }
   __device__ static float rnd(float x) { return x; }
-  __device__ static void unpack(u32x4 r, long long (&x)[V]) {
-    x[0] = __builtin_bit_cast(long long, u32x2{r[0], r[1]});
-    x[1] = __builtin_bit_cast(long long, u32x2{r[2], r[3]});
-  }
+  __device__ static void unpack(u32x4 r, long long* x) { El<FA_DTYPE_I64>::unpack(r, x); }
   __device__ static long long ld1(const void* p, int64_t e) { return ((const long long*)p)[e]; }
   __device__ static void st1(void* p, int64_t e, float v) { ((float*)p)[e] = v; }
   __device__ static void stv(void* p, const float (&a)[V]) {
@@ -205,10 +104,7 @@ template <> struct Tr<FA_DTYPE_I64, FA_MODE_SUM> {
   __device__ static D div(double) { return 0.f; }
   __device__ static A zero() { return 0ull; }
   __device__ static A rnd(A x) { return x; }
-  __device__ static void unpack(u32x4 r, long long (&x)[V]) {
-    x[0] = __builtin_bit_cast(long long, u32x2{r[0], r[1]});
-    x[1] = __builtin_bit_cast(long long, u32x2{r[2], r[3]});
-  }
+  __device__ static void unpack(u32x4 r, long long* x) { El<FA_DTYPE_I64>::unpack(r, x); }
   __device__ static long long ld1(const void* p, int64_t e) { return ((const long long*)p)[e]; }
   __device__ static void st1(void* p, int64_t e, A v) { ((unsigned long long*)p)[e] = v; }
   __device__ static void stv(void* p, const A (&a)[V]) {

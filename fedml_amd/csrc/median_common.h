@@ -1,14 +1,16 @@
 // median_common.h -- device helpers shared by the per-column kernels of the robust family
-// (median.hip: coordinate-wise median; trimmed.hip: coordinate-wise trimmed mean): raw global loads,
-// the 16-bit types' exact widening to float, the order-preserving float key, the segment record,
-// the flat / tile-interleaved column addressing.  Their common host path is median_host.h.  Not part
-// of the ABI.
+// (median.hip: coordinate-wise median; trimmed.hip: coordinate-wise trimmed mean; wsum_dist.hip: the
+// fused weighted sum and squared distances): raw global loads, the per-column element access, the
+// order-preserving float key, the segment record, the flat / tile-interleaved column addressing.
+// The conversions are elem.h's; the common host path is median_host.h.  Not part of the ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
+#include "elem.h"
 #include "fa_internal.h"
 
 namespace fa_detail {
@@ -33,45 +35,23 @@ __device__ __forceinline__ T gld_nt_off(const void* p, unsigned off) {
   return __builtin_nontemporal_load((const __attribute__((address_space(1))) T*)((const char*)p + off));
 }
 
-template <int DT> struct MedT;
-template <> struct MedT<FA_DTYPE_F32> {
-  using S = unsigned;
-  static constexpr int kBytes = 4;
-  __device__ static float load(const void* p, int64_t e) { return gld_nt<float>(p, e); }
-  __device__ static float load_off(const void* p, unsigned off) { return gld_nt_off<float>(p, off); }
-  __device__ static void store(void* p, int64_t e, float v) { ((float*)p)[e] = v; }
-  __device__ static void store_bits_off(void* p, int64_t e, const void* src, unsigned off) {
-    ((unsigned*)p)[e] = gld_nt_off<unsigned>(src, off);
-  }
-};
-template <> struct MedT<FA_DTYPE_BF16> {
-  static constexpr int kBytes = 2;
-  __device__ static float load(const void* p, int64_t e) {
-    return __uint_as_float((unsigned)gld_nt<unsigned short>(p, e) << 16);
-  }
-  __device__ static float load_off(const void* p, unsigned off) {
-    return __uint_as_float((unsigned)gld_nt_off<unsigned short>(p, off) << 16);
-  }
+// A column's element of a float dtype below float64: non-temporal loads widened exactly (elem.h),
+// the store of a value that came from the dtype, and a raw copy of a client's element.
+template <int DT> struct MedT {
+  using E = El<DT>;
+  using S = typename E::S;
+  static constexpr int kBytes = E::SZ;
+  __device__ static float load(const void* p, int64_t e) { return E::from_bits(gld_nt<S>(p, e)); }
+  __device__ static float load_off(const void* p, unsigned off) { return E::from_bits(gld_nt_off<S>(p, off)); }
+  // exact, v came from the dtype: no rounding, and no pin (elem.h's bits() would round bf16 and pin f16)
   __device__ static void store(void* p, int64_t e, float v) {
-    ((unsigned short*)p)[e] = (unsigned short)(__float_as_uint(v) >> 16);  // exact: v came from bf16
+    if constexpr (DT == FA_DTYPE_BF16) ((S*)p)[e] = (S)(__float_as_uint(v) >> 16);
+    else if constexpr (DT == FA_DTYPE_F16) ((S*)p)[e] = __builtin_bit_cast(S, (_Float16)v);
+    else ((S*)p)[e] = v;
   }
+  using W = typename std::conditional<sizeof(S) == 4, unsigned, S>::type;  // the element as an integer word
   __device__ static void store_bits_off(void* p, int64_t e, const void* src, unsigned off) {
-    ((unsigned short*)p)[e] = gld_nt_off<unsigned short>(src, off);
-  }
-};
-template <> struct MedT<FA_DTYPE_F16> {
-  static constexpr int kBytes = 2;
-  __device__ static float load(const void* p, int64_t e) {
-    return (float)__builtin_bit_cast(_Float16, gld_nt<unsigned short>(p, e));
-  }
-  __device__ static float load_off(const void* p, unsigned off) {
-    return (float)__builtin_bit_cast(_Float16, gld_nt_off<unsigned short>(p, off));
-  }
-  __device__ static void store(void* p, int64_t e, float v) {
-    ((unsigned short*)p)[e] = __builtin_bit_cast(unsigned short, (_Float16)v);  // exact: v came from f16
-  }
-  __device__ static void store_bits_off(void* p, int64_t e, const void* src, unsigned off) {
-    ((unsigned short*)p)[e] = gld_nt_off<unsigned short>(src, off);
+    ((W*)p)[e] = gld_nt_off<W>(src, off);
   }
 };
 
@@ -92,7 +72,7 @@ struct MSeg {
   void* out;
   int64_t tstride;  // 0: flat client segments; > 0: tile-interleaved inputs, bytes between a client's tiles
   int32_t ptr_base;
-  int32_t pad;
+  int32_t aligned;  // every input and the output are 16-byte aligned (read by wsum_dist.hip only)
 };
 static_assert(sizeof(MSeg) == 40, "MSeg layout");
 

@@ -1,7 +1,8 @@
-// median_host.h -- the host path shared by the C entries of the per-column operators (median.hip,
-// trimmed.hip): argument checks, the grid for a given columns-per-workgroup, the MSeg + pointer table
-// in a staging slot, and the launch.  An entry checks in this order: col_check_args (NULL context,
-// then the other arguments), its own arguments (the trim), col_launch (dtype, then tile_stride).
+// median_host.h -- the host path shared by the C entries that launch over an MSeg table (median.hip,
+// trimmed.hip, wsum_dist.hip): argument checks, the grid for a given element count per workgroup,
+// the MSeg + pointer table (and an entry's own payload) in a staging slot, and the launch.  An entry
+// checks in this order: col_check_args (NULL context, then the other arguments), its own arguments
+// (the trim; coef and d_stats), col_count (dtype, tile_stride, then the segments), its scratch.
 // Not part of the ABI.
 #pragma once
 
@@ -31,39 +32,47 @@ inline int col_check_args(const ColArgs& a) {
   return FA_OK;
 }
 
-// Checks the dtype, the tile stride and every non-empty segment's pointers, stages the segment and
-// pointer tables (skipped when the slot already holds them) and calls
-// launch(grid, stream, segs, nseg, ptrs) with `cols` columns per workgroup -- a count that divides
-// a tile's element count (512 float64 at the least), so no workgroup straddles a tile.
-template <class Launch>
-int col_launch(const ColArgs& a, int64_t cols, Launch launch) {
-  const int k = a.k;
+// Checks the dtype, the tile stride and every non-empty segment's pointers; counts the non-empty
+// segments and their workgroups at `cols` elements each -- a count that divides a tile's element
+// count (512 float64 at the least), so no workgroup straddles a tile.  (static: the library exports
+// nothing of this header)
+static inline int col_count(const ColArgs& a, int64_t cols, int* nseg, int64_t* tiles) {
   if (a.dtype != FA_DTYPE_F32 && a.dtype != FA_DTYPE_BF16 && a.dtype != FA_DTYPE_F16 && a.dtype != FA_DTYPE_F64)
     return fail(FA_ERR_DTYPE, "%s: dtype %d not supported (F32, BF16, F16, F64)", a.fn, a.dtype);
   if (a.tstride < 0 || a.tstride % FA_TILE_BYTES)
     return fail(FA_ERR_INVALID, "%s: tile_stride must be a positive multiple of %d (got %lld)", a.fn, FA_TILE_BYTES,
                 (long long)a.tstride);
-  int nseg = 0;
-  int64_t tiles = 0;
+  *nseg = 0;
+  *tiles = 0;
   for (int s = 0; s < a.num_segments; ++s) {
     if (a.seg_numel[s] < 0) return fail(FA_ERR_INVALID, "%s: segment %d has negative numel", a.fn, s);
     if (a.seg_numel[s] == 0) continue;
     if (!a.d_out[s]) return fail(FA_ERR_INVALID, "%s: segment %d: output NULL", a.fn, s);
-    for (int i = 0; i < k; ++i)
-      if (!a.d_in[(int64_t)s * k + i])
+    for (int i = 0; i < a.k; ++i)
+      if (!a.d_in[(int64_t)s * a.k + i])
         return fail(FA_ERR_INVALID, "%s: segment %d client %d: input NULL", a.fn, s, i);
-    ++nseg;
-    tiles += (a.seg_numel[s] + cols - 1) / cols;
+    ++*nseg;
+    *tiles += (a.seg_numel[s] + cols - 1) / cols;
   }
-  if (nseg == 0) return FA_OK;
-  if (tiles > 0x7FFFFFFFll) return fail(FA_ERR_INVALID, "%s: too many tiles", a.fn);
+  if (*tiles > 0x7FFFFFFFll) return fail(FA_ERR_INVALID, "%s: too many tiles", a.fn);
+  return FA_OK;
+}
+
+// After col_count found nseg > 0 segments and `tiles` workgroups: stages the segment and pointer
+// tables of the non-empty segments, followed by `extra` bytes (8-byte aligned) that fill(host
+// address) writes (the copy is skipped when the slot already holds all of it), and calls
+// launch(grid, stream, segs, nseg, ptrs, the payload's device address).
+template <class Fill, class Launch>
+int col_stage_launch(const ColArgs& a, int64_t cols, int nseg, int64_t tiles, size_t extra, Fill fill,
+                     Launch launch) {
+  const int k = a.k;
   const size_t seg_bytes = align16(sizeof(MSeg) * nseg);
   const size_t ptr_bytes = sizeof(void*) * (size_t)nseg * k;
   DeviceGuard g(a.ctx->device);
   if (!g.ok) return fail(FA_ERR_HIP, "hipSetDevice(%d) failed", a.ctx->device);
   hipStream_t st = (hipStream_t)a.hip_stream;
   fa_ctx::Slot* slot = nullptr;
-  int rc = acquire_slot(a.ctx, seg_bytes + ptr_bytes, &slot);
+  int rc = acquire_slot(a.ctx, seg_bytes + ptr_bytes + extra, &slot);
   if (rc) return rc;
   char* h = (char*)slot->host;
   MSeg* hs = (MSeg*)h;
@@ -73,21 +82,41 @@ int col_launch(const ColArgs& a, int64_t cols, Launch launch) {
   for (int s = 0; s < a.num_segments; ++s) {
     const int64_t n = a.seg_numel[s];
     if (n == 0) continue;
-    for (int i = 0; i < k; ++i) hp[(int64_t)j * k + i] = a.d_in[(int64_t)s * k + i];
-    hs[j] = MSeg{n, t0, a.d_out[s], a.tstride, j * k, 0};
+    bool aligned = al16(a.d_out[s]);
+    for (int i = 0; i < k; ++i) {
+      hp[(int64_t)j * k + i] = a.d_in[(int64_t)s * k + i];
+      aligned = aligned && al16(a.d_in[(int64_t)s * k + i]);
+    }
+    hs[j] = MSeg{n, t0, a.d_out[s], a.tstride, j * k, aligned ? 1 : 0};
     t0 += (n + cols - 1) / cols;
     ++j;
   }
-  rc = stage(slot, seg_bytes + ptr_bytes, st, true);
+  fill((void*)(h + seg_bytes + ptr_bytes));
+  rc = stage(slot, seg_bytes + ptr_bytes + extra, st, true);
   if (rc) return rc;
   const char* dv = (const char*)slot->dev;
-  launch(dim3((unsigned)tiles), st, (const MSeg*)dv, nseg, (const void* const*)(dv + seg_bytes));
+  launch(dim3((unsigned)tiles), st, (const MSeg*)dv, nseg, (const void* const*)(dv + seg_bytes),
+         (const void*)(dv + seg_bytes + ptr_bytes));
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     (void)release(slot, st);
     return fail(FA_ERR_HIP, "%s: %s", a.fn, hipGetErrorString(e));
   }
   return release(slot, st);
+}
+
+// The two steps for an entry with nothing of its own between them or in the slot (no segment with
+// elements: nothing to do).  launch(grid, stream, segs, nseg, ptrs).
+template <class Launch>
+int col_launch(const ColArgs& a, int64_t cols, Launch launch) {
+  int nseg;
+  int64_t tiles;
+  if (const int rc = col_count(a, cols, &nseg, &tiles)) return rc;
+  if (nseg == 0) return FA_OK;
+  return col_stage_launch(a, cols, nseg, tiles, 0, [](void*) {},
+                          [&](dim3 grid, hipStream_t st, const MSeg* ds, int n, const void* const* dp, const void*) {
+                            launch(grid, st, ds, n, dp);
+                          });
 }
 
 }  // namespace fa_detail

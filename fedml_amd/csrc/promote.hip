@@ -15,33 +15,19 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "elem.h"
 #include "fa_internal.h"
 
 using namespace fa_detail;
 
 namespace {
 
-__device__ __forceinline__ float pin(float x) {  // keep the f32 intermediate (no fused f32->f16 paths)
-  asm("" : "+v"(x));
-  return x;
+// element e of a tensor of dtype DT, widened exactly (float for f32/bf16/f16, double for f64, int64
+// as is)
+template <int DT>
+__device__ __forceinline__ typename El<DT>::A ld(const void* p, int64_t e) {
+  return El<DT>::from_bits(((const typename El<DT>::S*)p)[e]);
 }
-__device__ __forceinline__ float rnd_bf16(float x) { return (float)(__bf16)pin(x); }
-__device__ __forceinline__ float rnd_f16(float x) { return (float)(_Float16)pin(x); }
-
-// value of element e of a tensor of dtype DT, widened exactly (float for f32/bf16/f16, double for
-// f64, int64 as is)
-template <int DT> struct Ld;
-template <> struct Ld<FA_DTYPE_F32> { using T = float; __device__ static T get(const void* p, int64_t e) { return ((const float*)p)[e]; } };
-template <> struct Ld<FA_DTYPE_F64> { using T = double; __device__ static T get(const void* p, int64_t e) { return ((const double*)p)[e]; } };
-template <> struct Ld<FA_DTYPE_I64> { using T = long long; __device__ static T get(const void* p, int64_t e) { return ((const long long*)p)[e]; } };
-template <> struct Ld<FA_DTYPE_BF16> {
-  using T = float;
-  __device__ static T get(const void* p, int64_t e) { return __uint_as_float((unsigned)((const unsigned short*)p)[e] << 16); }
-};
-template <> struct Ld<FA_DTYPE_F16> {
-  using T = float;
-  __device__ static T get(const void* p, int64_t e) { return (float)__builtin_bit_cast(_Float16, ((const unsigned short*)p)[e]); }
-};
 
 // PyTorch's promote_types for the pairs that reach this kernel (acc a float dtype)
 template <int A, int B>
@@ -51,39 +37,33 @@ constexpr int promoted() {
   return FA_DTYPE_F32;  // f32 with anything below it, and bf16 with f16
 }
 
-// c10 cast of an exactly-widened value to dtype C (returned in C's op-math type)
+// x itself; before a rounding to bf16 pinned as an f32 in a register (elem.h: pin_f32, which the f16
+// rounding there applies itself): without the pin hipcc compiles this kernel's bf16 forms to another,
+// four times longer instruction stream
+template <int C, class X>
+__device__ __forceinline__ X pinned(X x) {
+  if constexpr (C == FA_DTYPE_BF16) return pin_f32(x);
+  else return x;
+}
+
+// c10 cast of an exactly-widened value to dtype C (returned in C's op-math type): to double float ->
+// double is exact and int64 correctly rounded; to the float types THROUGH float32 (float types exact,
+// int64 correctly rounded; no f64 here), then rounded once to C
 template <int C, class V>
-__device__ __forceinline__ auto to_common(V v) {
-  if constexpr (C == FA_DTYPE_F64) {
-    return (double)v;  // float -> double exact; int64 -> double correctly rounded
-  } else {
-    const float f = (float)v;  // float types exact; int64 -> float correctly rounded; (no f64 here)
-    if constexpr (C == FA_DTYPE_BF16) return rnd_bf16(f);
-    else if constexpr (C == FA_DTYPE_F16) return rnd_f16(f);
-    else return f;
-  }
+__device__ __forceinline__ typename El<C>::A to_common(V v) {
+  return El<C>::rnd(pinned<C>((typename El<C>::A)v));
 }
 
 // C's add, rounded to C
 template <int C, class V>
 __device__ __forceinline__ V add_in(V a, V b) {
-  if constexpr (C == FA_DTYPE_F64) return __dadd_rn(a, b);
-  else if constexpr (C == FA_DTYPE_BF16) return rnd_bf16(__fadd_rn(a, b));
-  else if constexpr (C == FA_DTYPE_F16) return rnd_f16(__fadd_rn(a, b));
-  else return __fadd_rn(a, b);
+  return El<C>::rnd(pinned<C>(op_add(a, b)));
 }
 
-// c10 cast of a C value to the accumulator dtype A, stored
+// c10 cast of a C value to the accumulator dtype A (double -> float rounds first), stored
 template <int A, class V>
 __device__ __forceinline__ void store(void* p, int64_t e, V v) {
-  if constexpr (A == FA_DTYPE_F64) {
-    ((double*)p)[e] = (double)v;
-  } else {
-    const float f = (float)v;  // double -> float (round), float -> float
-    if constexpr (A == FA_DTYPE_F32) ((float*)p)[e] = f;
-    else if constexpr (A == FA_DTYPE_BF16) ((unsigned short*)p)[e] = __builtin_bit_cast(unsigned short, (__bf16)pin(f));
-    else ((unsigned short*)p)[e] = __builtin_bit_cast(unsigned short, (_Float16)pin(f));
-  }
+  ((typename El<A>::S*)p)[e] = El<A>::bits(pinned<A>((typename El<A>::A)v));
 }
 
 template <int A, int B>
@@ -92,8 +72,8 @@ __global__ void __launch_bounds__(kBlock) k_promote_add(const void* __restrict__
   constexpr int C = promoted<A, B>();
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < n; e += stride) {
-    const auto a = to_common<C>(Ld<A>::get(acc, e));
-    const auto b = to_common<C>(Ld<B>::get(t, e));
+    const auto a = to_common<C>(ld<A>(acc, e));
+    const auto b = to_common<C>(ld<B>(t, e));
     store<A>(out, e, add_in<C>(a, b));
   }
 }

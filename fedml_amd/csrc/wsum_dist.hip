@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "elem.h"
 #include "fa_internal.h"
 #include "fedagg_robust.h"
 #include "median_common.h"
@@ -36,97 +37,16 @@ using namespace fa_detail;
 
 namespace {
 
-// ----- the weighted sum's arithmetic (fedagg.hip, "Exact per-op arithmetic" and Tr<DT, MUL_W>) -----
-__device__ __forceinline__ float op_mul(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ float op_add(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ float op_sub(float a, float b) { return __fsub_rn(a, b); }
-__device__ __forceinline__ double op_mul(double a, double b) { return __dmul_rn(a, b); }
-__device__ __forceinline__ double op_add(double a, double b) { return __dadd_rn(a, b); }
-__device__ __forceinline__ double op_sub(double a, double b) { return __dsub_rn(a, b); }
-// the f32 -> f16 rounding must see a materialised f32 (else the backend folds the product's two
-// roundings into one v_fma_mixlo_f16; fedagg.hip pin_f32)
-__device__ __forceinline__ float pin_f32(float x) {
-  asm("" : "+v"(x));
-  return x;
+// The weighted sum's arithmetic and conversions are elem.h's, the ones fedagg.hip's FA_MODE_MUL_W
+// uses; only the element accessors are this file's: global address space, plain stores.
+template <int DT>
+__device__ __forceinline__ typename El<DT>::A ld1(const void* p, int64_t e) {
+  return El<DT>::from_bits(gld<typename El<DT>::S>(p, e));
 }
-
-template <int DT> struct WT;
-template <> struct WT<FA_DTYPE_F32> {
-  using A = float;
-  static constexpr int V = 4, SZ = 4;
-  __device__ static float rnd(float x) { return x; }
-  __device__ static void unpack(u32x4 r, float* x) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) x[j] = __uint_as_float(r[j]);
-  }
-  __device__ static u32x4 pack(const float* a) {
-    return u32x4{__float_as_uint(a[0]), __float_as_uint(a[1]), __float_as_uint(a[2]), __float_as_uint(a[3])};
-  }
-  __device__ static float ld1(const void* p, int64_t e) { return gld<float>(p, e); }
-  __device__ static void st1(void* p, int64_t e, float v) { ((float*)p)[e] = v; }
-};
-template <> struct WT<FA_DTYPE_BF16> {
-  using A = float;
-  static constexpr int V = 8, SZ = 2;
-  __device__ static float rnd(float x) { return (float)(__bf16)x; }
-  __device__ static unsigned bits(float x) { return (unsigned)__builtin_bit_cast(unsigned short, (__bf16)x); }
-  __device__ static void unpack(u32x4 r, float* x) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      x[2 * j] = __uint_as_float(r[j] << 16);
-      x[2 * j + 1] = __uint_as_float(r[j] & 0xFFFF0000u);
-    }
-  }
-  __device__ static u32x4 pack(const float* a) {
-    u32x4 w;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) w[j] = bits(a[2 * j]) | (bits(a[2 * j + 1]) << 16);
-    return w;
-  }
-  __device__ static float ld1(const void* p, int64_t e) {
-    return __uint_as_float((unsigned)gld<unsigned short>(p, e) << 16);
-  }
-  __device__ static void st1(void* p, int64_t e, float v) { ((unsigned short*)p)[e] = (unsigned short)bits(v); }
-};
-template <> struct WT<FA_DTYPE_F16> {
-  using A = float;
-  static constexpr int V = 8, SZ = 2;
-  __device__ static float rnd(float x) { return (float)(_Float16)pin_f32(x); }
-  __device__ static unsigned bits(float x) {
-    return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)pin_f32(x));
-  }
-  __device__ static float from_bits(unsigned b) { return (float)__builtin_bit_cast(_Float16, (unsigned short)b); }
-  __device__ static void unpack(u32x4 r, float* x) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      x[2 * j] = from_bits(r[j] & 0xFFFFu);
-      x[2 * j + 1] = from_bits(r[j] >> 16);
-    }
-  }
-  __device__ static u32x4 pack(const float* a) {
-    u32x4 w;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) w[j] = bits(a[2 * j]) | (bits(a[2 * j + 1]) << 16);
-    return w;
-  }
-  __device__ static float ld1(const void* p, int64_t e) { return from_bits(gld<unsigned short>(p, e)); }
-  __device__ static void st1(void* p, int64_t e, float v) { ((unsigned short*)p)[e] = (unsigned short)bits(v); }
-};
-template <> struct WT<FA_DTYPE_F64> {
-  using A = double;
-  static constexpr int V = 2, SZ = 8;
-  __device__ static double rnd(double x) { return x; }
-  __device__ static void unpack(u32x4 r, double* x) {
-    x[0] = __builtin_bit_cast(double, u32x2{r[0], r[1]});
-    x[1] = __builtin_bit_cast(double, u32x2{r[2], r[3]});
-  }
-  __device__ static u32x4 pack(const double* a) {
-    const u32x2 lo = __builtin_bit_cast(u32x2, a[0]), hi = __builtin_bit_cast(u32x2, a[1]);
-    return u32x4{lo[0], lo[1], hi[0], hi[1]};
-  }
-  __device__ static double ld1(const void* p, int64_t e) { return gld<double>(p, e); }
-  __device__ static void st1(void* p, int64_t e, double v) { ((double*)p)[e] = v; }
-};
+template <int DT>
+__device__ __forceinline__ void st1(void* p, int64_t e, typename El<DT>::A v) {
+  ((typename El<DT>::S*)p)[e] = El<DT>::bits(v);
+}
 
 constexpr int kS = 4;     // 4-KiB slots per client and workgroup
 constexpr int kKB = 128;  // clients per pass of phase 2 (the LDS block of wave sums)
@@ -172,7 +92,7 @@ __device__ __forceinline__ void flush_rows(double (&red)[kRows][2 * kKB], int b0
 // lane l is the chunk's element j * kBlock + l).
 template <int DT, bool VEC>
 struct Chunk {
-  using T = WT<DT>;
+  using T = El<DT>;
   using A = typename T::A;
   static constexpr int V = T::V, NE = kS * V;
   static constexpr int64_t E = FA_TILE_BYTES / T::SZ;
@@ -187,7 +107,7 @@ struct Chunk {
       for (int s = 0; s < kS; ++s) r[s] = *(const __attribute__((address_space(1))) u32x4*)((const char*)p + off[s]);
     } else {
 #pragma unroll
-      for (int j = 0; j < NE; ++j) r[j] = T::ld1(p, off[j]);
+      for (int j = 0; j < NE; ++j) r[j] = ld1<DT>(p, off[j]);
     }
   }
   __device__ static void get(const Raw (&r)[NR], A (&x)[NE]) {
@@ -206,7 +126,7 @@ __device__ __forceinline__ void wsd_chunk(const MSeg& sg, int64_t tl, const void
                                           const double* __restrict__ coef, int k, double* __restrict__ part,
                                           double (&red)[kRows][2 * kKB]) {
   using C = Chunk<DT, VEC>;
-  using T = WT<DT>;
+  using T = El<DT>;
   using A = typename T::A;
   constexpr int V = T::V, NE = C::NE, NR = C::NR;
   constexpr int64_t E = C::E;
@@ -276,7 +196,7 @@ __device__ __forceinline__ void wsd_chunk(const MSeg& sg, int64_t tl, const void
   } else {
 #pragma unroll
     for (int j = 0; j < NE; ++j)
-      if (live >> j & 1u) T::st1(sg.out, e0 + (int64_t)j * kBlock + tid, acc[j]);
+      if (live >> j & 1u) st1<DT>(sg.out, e0 + (int64_t)j * kBlock + tid, acc[j]);
   }
 
   // phase 2: the two sums of every client against the registers' out, kKB clients per LDS block
@@ -319,13 +239,13 @@ __global__ void __launch_bounds__(kBlock)
 k_wsd(const MSeg* __restrict__ segs, int nseg, const void* const* __restrict__ ptrs,
       const double* __restrict__ coef, int k, double* __restrict__ partial) {
   __shared__ double red[kRows][2 * kKB];
-  constexpr int64_t CH = kS * (FA_TILE_BYTES / WT<DT>::SZ);  // elements per chunk
+  constexpr int64_t CH = kS * (FA_TILE_BYTES / El<DT>::SZ);  // elements per chunk
   const int64_t tile = blockIdx.x;
   const MSeg sg = segs[nseg > 1 ? find_seg(segs, nseg, tile) : 0];
   const int64_t tl = tile - sg.tile_start;
   const void* const* in = ptrs + sg.ptr_base;
   double* part = partial + tile * (2 * (int64_t)k);
-  if (sg.pad && (tl + 1) * CH <= sg.numel)  // pad: the segment's inputs and output are 16-byte aligned
+  if (sg.aligned && (tl + 1) * CH <= sg.numel)
     wsd_chunk<DT, true>(sg, tl, in, coef, k, part, red);
   else
     wsd_chunk<DT, false>(sg, tl, in, coef, k, part, red);
@@ -343,7 +263,7 @@ template <int DT, int KM>
 __global__ void __launch_bounds__(kBlock)
 k_wsd_reg(const MSeg* __restrict__ segs, int nseg, const void* const* __restrict__ ptrs,
           const double* __restrict__ coef, int k, double* __restrict__ partial) {
-  using T = WT<DT>;
+  using T = El<DT>;
   using A = typename T::A;
   constexpr int V = T::V;
   constexpr int64_t E = FA_TILE_BYTES / T::SZ, CH = kS * E;
@@ -353,7 +273,7 @@ k_wsd_reg(const MSeg* __restrict__ segs, int nseg, const void* const* __restrict
   const int64_t tl = tile - sg.tile_start;
   const void* const* in = ptrs + sg.ptr_base;
   double* part = partial + tile * (2 * (int64_t)k);
-  if (!(sg.pad && (tl + 1) * CH <= sg.numel)) {
+  if (!(sg.aligned && (tl + 1) * CH <= sg.numel)) {
     wsd_chunk<DT, false>(sg, tl, in, coef, k, part, red);
     return;
   }
@@ -447,106 +367,52 @@ int64_t chunk_elems(int dtype) {
   return (int64_t)kS * (FA_TILE_BYTES / (dtype == FA_DTYPE_F64 ? 8 : dtype == FA_DTYPE_F32 ? 4 : 2));
 }
 
-// chunks of the non-empty segments (-1: a negative numel)
-int64_t count_chunks(int32_t num_segments, const int64_t* seg_numel, int64_t ch) {
-  int64_t tiles = 0;
-  for (int s = 0; s < num_segments; ++s) {
-    if (seg_numel[s] < 0) return -1;
-    tiles += (seg_numel[s] + ch - 1) / ch;
-  }
-  return tiles;
-}
-
 int wsd_impl(const ColArgs& a, const double* coef, void* d_stats, void* d_scratch, size_t scratch_bytes) {
   if (const int rc = col_check_args(a)) return rc;
   const int k = a.k;
   if (!coef) return fail(FA_ERR_INVALID, "%s: coef is NULL", a.fn);
   if (!d_stats) return fail(FA_ERR_INVALID, "%s: d_stats is NULL", a.fn);
-  if (a.dtype != FA_DTYPE_F32 && a.dtype != FA_DTYPE_BF16 && a.dtype != FA_DTYPE_F16 && a.dtype != FA_DTYPE_F64)
-    return fail(FA_ERR_DTYPE, "%s: dtype %d not supported (F32, BF16, F16, F64)", a.fn, a.dtype);
-  if (a.tstride < 0 || a.tstride % FA_TILE_BYTES)
-    return fail(FA_ERR_INVALID, "%s: tile_stride must be a positive multiple of %d (got %lld)", a.fn, FA_TILE_BYTES,
-                (long long)a.tstride);
   const int64_t ch = chunk_elems(a.dtype);
-  int nseg = 0;
-  for (int s = 0; s < a.num_segments; ++s) {
-    if (a.seg_numel[s] < 0) return fail(FA_ERR_INVALID, "%s: segment %d has negative numel", a.fn, s);
-    if (a.seg_numel[s] == 0) continue;
-    if (!a.d_out[s]) return fail(FA_ERR_INVALID, "%s: segment %d: output NULL", a.fn, s);
-    for (int i = 0; i < k; ++i)
-      if (!a.d_in[(int64_t)s * k + i])
-        return fail(FA_ERR_INVALID, "%s: segment %d client %d: input NULL", a.fn, s, i);
-    ++nseg;
-  }
-  const int64_t tiles = count_chunks(a.num_segments, a.seg_numel, ch);
-  if (tiles > 0x7FFFFFFFll) return fail(FA_ERR_INVALID, "%s: too many chunks", a.fn);
+  int nseg;
+  int64_t tiles;
+  if (const int rc = col_count(a, ch, &nseg, &tiles)) return rc;
   const size_t need = (size_t)tiles * 2 * (size_t)k * sizeof(double);
   if (need > scratch_bytes || (need && !d_scratch))
     return fail(FA_ERR_INVALID, "%s: scratch too small (%zu bytes, need %zu)", a.fn, d_scratch ? scratch_bytes : (size_t)0,
                 need);
-  DeviceGuard g(a.ctx->device);
-  if (!g.ok) return fail(FA_ERR_HIP, "hipSetDevice(%d) failed", a.ctx->device);
-  hipStream_t st = (hipStream_t)a.hip_stream;
   if (nseg == 0) {  // nothing to read: every sum is 0
-    FA_HIP(hipMemsetAsync(d_stats, 0, sizeof(double) * 2 * (size_t)k, st));
+    DeviceGuard g(a.ctx->device);
+    if (!g.ok) return fail(FA_ERR_HIP, "hipSetDevice(%d) failed", a.ctx->device);
+    FA_HIP(hipMemsetAsync(d_stats, 0, sizeof(double) * 2 * (size_t)k, (hipStream_t)a.hip_stream));
     return FA_OK;
   }
-  const size_t seg_bytes = align16(sizeof(MSeg) * nseg);
-  const size_t ptr_bytes = align16(sizeof(void*) * (size_t)nseg * k);
-  const size_t coef_bytes = sizeof(double) * (size_t)k;
-  fa_ctx::Slot* slot = nullptr;
-  int rc = acquire_slot(a.ctx, seg_bytes + ptr_bytes + coef_bytes, &slot);
-  if (rc) return rc;
-  char* h = (char*)slot->host;
-  MSeg* hs = (MSeg*)h;
-  const void** hp = (const void**)(h + seg_bytes);
-  double* hc = (double*)(h + seg_bytes + ptr_bytes);
-  int j = 0;
-  int64_t t0 = 0;
-  for (int s = 0; s < a.num_segments; ++s) {
-    const int64_t n = a.seg_numel[s];
-    if (n == 0) continue;
-    bool aligned = al16(a.d_out[s]);
-    for (int i = 0; i < k; ++i) {
-      hp[(int64_t)j * k + i] = a.d_in[(int64_t)s * k + i];
-      aligned = aligned && al16(a.d_in[(int64_t)s * k + i]);
-    }
-    hs[j] = MSeg{n, t0, a.d_out[s], a.tstride, j * k, aligned ? 1 : 0};
-    t0 += (n + ch - 1) / ch;
-    ++j;
-  }
-  for (int i = 0; i < k; ++i) hc[i] = coef[i];
-  rc = stage(slot, seg_bytes + ptr_bytes + coef_bytes, st, true);
-  if (rc) return rc;
-  const char* dv = (const char*)slot->dev;
-  const MSeg* ds = (const MSeg*)dv;
-  const void* const* dp = (const void* const*)(dv + seg_bytes);
-  const double* dc = (const double*)(dv + seg_bytes + ptr_bytes);
   double* part = (double*)d_scratch;
-  const dim3 grid((unsigned)tiles), block(kBlock);
-  if (a.dtype == FA_DTYPE_F32 && k <= kRegMaxK && wsd_reg_enabled()) {
-    switch ((k + 7) / 8) {  // KM = K rounded up to 8
+  return col_stage_launch(
+      a, ch, nseg, tiles, sizeof(double) * (size_t)k,
+      [&](void* h) {
+        for (int i = 0; i < k; ++i) ((double*)h)[i] = coef[i];
+      },
+      [&](dim3 grid, hipStream_t st, const MSeg* ds, int n, const void* const* dp, const void* payload) {
+        const double* dc = (const double*)payload;
+        const dim3 block(kBlock);
+        if (a.dtype == FA_DTYPE_F32 && k <= kRegMaxK && wsd_reg_enabled()) {
+          switch ((k + 7) / 8) {  // KM = K rounded up to 8
 #define FA_WR(Q) \
-  case Q: hipLaunchKernelGGL((k_wsd_reg<FA_DTYPE_F32, 8 * Q>), grid, block, 0, st, ds, nseg, dp, dc, k, part); break;
-      FA_WR(1) FA_WR(2) FA_WR(3) FA_WR(4)
+  case Q: hipLaunchKernelGGL((k_wsd_reg<FA_DTYPE_F32, 8 * Q>), grid, block, 0, st, ds, n, dp, dc, k, part); break;
+            FA_WR(1) FA_WR(2) FA_WR(3) FA_WR(4)
 #undef FA_WR
-    }
-  } else {
-    switch (a.dtype) {
-      case FA_DTYPE_F32: hipLaunchKernelGGL((k_wsd<FA_DTYPE_F32>), grid, block, 0, st, ds, nseg, dp, dc, k, part); break;
-      case FA_DTYPE_BF16: hipLaunchKernelGGL((k_wsd<FA_DTYPE_BF16>), grid, block, 0, st, ds, nseg, dp, dc, k, part); break;
-      case FA_DTYPE_F16: hipLaunchKernelGGL((k_wsd<FA_DTYPE_F16>), grid, block, 0, st, ds, nseg, dp, dc, k, part); break;
-      default: hipLaunchKernelGGL((k_wsd<FA_DTYPE_F64>), grid, block, 0, st, ds, nseg, dp, dc, k, part); break;
-    }
-  }
-  hipLaunchKernelGGL(k_wsd_reduce, dim3((unsigned)((2 * k + kRE - 1) / kRE)), dim3(64 * kRW), 0, st,
-                     (const double*)part, tiles, 2 * k, (double*)d_stats);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    (void)release(slot, st);
-    return fail(FA_ERR_HIP, "%s: %s", a.fn, hipGetErrorString(e));
-  }
-  return release(slot, st);
+          }
+        } else {
+          switch (a.dtype) {
+            case FA_DTYPE_F32: hipLaunchKernelGGL((k_wsd<FA_DTYPE_F32>), grid, block, 0, st, ds, n, dp, dc, k, part); break;
+            case FA_DTYPE_BF16: hipLaunchKernelGGL((k_wsd<FA_DTYPE_BF16>), grid, block, 0, st, ds, n, dp, dc, k, part); break;
+            case FA_DTYPE_F16: hipLaunchKernelGGL((k_wsd<FA_DTYPE_F16>), grid, block, 0, st, ds, n, dp, dc, k, part); break;
+            default: hipLaunchKernelGGL((k_wsd<FA_DTYPE_F64>), grid, block, 0, st, ds, n, dp, dc, k, part); break;
+          }
+        }
+        hipLaunchKernelGGL(k_wsd_reduce, dim3((unsigned)((2 * k + kRE - 1) / kRE)), dim3(64 * kRW), 0, st,
+                           (const double*)part, tiles, 2 * k, (double*)d_stats);
+      });
 }
 
 }  // namespace
@@ -572,8 +438,13 @@ int fa_weighted_sum_sqdist_tiled(fa_ctx* ctx, int dtype, int32_t num_segments, c
 // The per-chunk rows of the smallest chunk any dtype uses (float64's), so one size serves every dtype.
 size_t fa_weighted_sum_sqdist_scratch_bytes(int32_t num_segments, const int64_t* seg_numel, int32_t k) {
   if (k <= 0 || num_segments <= 0 || !seg_numel) return 0;
-  const int64_t tiles = count_chunks(num_segments, seg_numel, chunk_elems(FA_DTYPE_F64));
-  if (tiles < 0 || tiles > 0x7FFFFFFFll) return 0;
+  const int64_t ch = chunk_elems(FA_DTYPE_F64);
+  int64_t tiles = 0;
+  for (int s = 0; s < num_segments; ++s) {
+    if (seg_numel[s] < 0) return 0;
+    tiles += (seg_numel[s] + ch - 1) / ch;
+  }
+  if (tiles > 0x7FFFFFFFll) return 0;
   return (size_t)tiles * 2 * (size_t)k * sizeof(double);
 }
 

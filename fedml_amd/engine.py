@@ -864,16 +864,19 @@ class AggEngine:
             raise ValueError(f"{what}: trim must be an integer with 0 <= trim and 2 * trim < K (trim {trim}, K {k})")
         return int(trim)
 
-    def _column_op(self, what: str, segments, outs, stream, *trim) -> List[torch.Tensor]:
-        """The flat per-column operators (``what`` = coord_median, or coord_trimmed_mean followed by
-        its ``trim``): validates the segments, builds pointers, sizes and outputs, one launch of fa_<what>."""
+    def _check_column_dtype(self, what: str, dt) -> None:
+        if dt not in self._COLUMN_DTYPES:
+            raise TypeError(f"{what}: unsupported dtype {dt}")
+
+    def _flat_segments(self, what: str, segments, outs):
+        """The flat entries over an MSeg table: validates the client count, the dtype, every client's
+        dtype, shape and device and the given outputs (allocates them otherwise).
+        Returns (dtype, K, input pointers, element counts, outputs)."""
         k = len(segments[0]) if segments else 0
         if k == 0:
             raise ValueError(f"{what}: no client tensors")
         dt = segments[0][0].dtype
-        if dt not in self._COLUMN_DTYPES:
-            raise TypeError(f"{what}: unsupported dtype {dt}")
-        trim = [self._check_trim(b, k, what) for b in trim]
+        self._check_column_dtype(what, dt)
         in_ptrs, numels, results = [], [], []
         for s, seg in enumerate(segments):
             if len(seg) != k:
@@ -892,6 +895,22 @@ class AggEngine:
                 o = torch.empty(seg[0].shape, dtype=dt, device=self.device)
             results.append(o)
             numels.append(seg[0].numel())
+        return dt, k, in_ptrs, numels, results
+
+    def _tiled_out(self, what: str, buf: torch.Tensor, n: int, out: Optional[torch.Tensor]) -> torch.Tensor:
+        """The given output of a tiled entry, checked, or a new one: flat, ``n`` elements of buf's dtype."""
+        if out is None:
+            out = torch.empty(n, dtype=buf.dtype, device=self.device)
+        elif out.dtype != buf.dtype or out.numel() != n or not out.is_contiguous():
+            raise ValueError(f"{what}: output must be a contiguous {buf.dtype} tensor of {n} elements")
+        _require_device(out, self.device, "output")
+        return out
+
+    def _column_op(self, what: str, segments, outs, stream, *trim) -> List[torch.Tensor]:
+        """The flat per-column operators (``what`` = coord_median, or coord_trimmed_mean followed by
+        its ``trim``): one launch of fa_<what>."""
+        dt, k, in_ptrs, numels, results = self._flat_segments(what, segments, outs)
+        trim = [self._check_trim(b, k, what) for b in trim]
         rc = getattr(self._lib, "fa_" + what)(self._ctx, DTYPE_CODE[dt], len(segments), N.i64_array(numels), k, *trim,
                                               N.ptr_array(in_ptrs), N.ptr_array([o.data_ptr() for o in results]),
                                               self._stream(stream))
@@ -901,15 +920,10 @@ class AggEngine:
     def _column_op_tiled(self, what: str, buf: torch.Tensor, rows, n, out, stream, *trim) -> torch.Tensor:
         """The tiled per-column operators (``what`` = coord_median_tiled, or coord_trimmed_mean_tiled
         followed by its ``trim``) over rows of a tile-interleaved arena group: one launch of fa_<what>."""
-        if buf.dtype not in self._COLUMN_DTYPES:
-            raise TypeError(f"{what}: unsupported dtype {buf.dtype}")
+        self._check_column_dtype(what, buf.dtype)
         trim = [self._check_trim(b, len(rows), what) for b in trim]
         n, ptrs, stride = self._tiled_args(buf, rows, 0, n, what)
-        if out is None:
-            out = torch.empty(n, dtype=buf.dtype, device=self.device)
-        elif out.dtype != buf.dtype or out.numel() != n or not out.is_contiguous():
-            raise ValueError(f"{what}: output must be a contiguous {buf.dtype} tensor of {n} elements")
-        _require_device(out, self.device, "output")
+        out = self._tiled_out(what, buf, n, out)
         if n == 0:
             return out
         rc = getattr(self._lib, "fa_" + what)(self._ctx, DTYPE_CODE[buf.dtype], 1, N.i64_array([n]), len(rows), *trim,
@@ -960,31 +974,8 @@ class AggEngine:
         segments[s][i] = client i's tensor of segment s (one dtype: float32, bfloat16, float16,
         float64); one launch.  Returns (outs, stats)."""
         what = "weighted_sum_sqdist"
-        k = len(segments[0]) if segments else 0
-        if k == 0:
-            raise ValueError(f"{what}: no client tensors")
-        dt = segments[0][0].dtype
-        if dt not in self._COLUMN_DTYPES:
-            raise TypeError(f"{what}: unsupported dtype {dt}")
+        dt, k, in_ptrs, numels, results = self._flat_segments(what, segments, outs)
         c = self._sqdist_coef(what, coef, k)
-        in_ptrs, numels, results = [], [], []
-        for s, seg in enumerate(segments):
-            if len(seg) != k:
-                raise ValueError(f"segment {s}: {len(seg)} clients, expected {k}")
-            for i, t in enumerate(seg):
-                if t.dtype != dt or t.shape != seg[0].shape:
-                    raise ValueError(f"segment {s} client {i}: dtype/shape mismatch")
-                _require_device(t, self.device, f"segment {s} client {i}")
-                in_ptrs.append(t.data_ptr())
-            if outs is not None:
-                o = outs[s]
-                if o.dtype != dt or o.numel() != seg[0].numel():
-                    raise ValueError(f"segment {s}: output must be {dt} with {seg[0].numel()} elements")
-                _require_device(o, self.device, f"segment {s} output")
-            else:
-                o = torch.empty(seg[0].shape, dtype=dt, device=self.device)
-            results.append(o)
-            numels.append(seg[0].numel())
         nm = N.i64_array(numels)
         need = int(self._lib.fa_weighted_sum_sqdist_scratch_bytes(len(segments), nm, k))
         scratch = self._scratch("wsum_sqdist", need, stream)
@@ -1000,18 +991,14 @@ class AggEngine:
                                   stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """``weighted_sum_sqdist`` over rows of a TILE-INTERLEAVED arena group ``buf`` [tiles, capacity,
         E] (fa_weighted_sum_sqdist_tiled): the same out, bit for bit, as over the logical rows.
-        Returns (out, stats); out is flat, ``n`` elements (default: all)."""
+        Returns (out, stats); out is flat, ``n`` elements (default: all).  n == 0 still makes the
+        native call: it zeroes the stats."""
         what = "weighted_sum_sqdist_tiled"
-        if buf.dtype not in self._COLUMN_DTYPES:
-            raise TypeError(f"{what}: unsupported dtype {buf.dtype}")
+        self._check_column_dtype(what, buf.dtype)
         n, ptrs, stride = self._tiled_args(buf, rows, 0, n, what)
         k = len(rows)
         c = self._sqdist_coef(what, coef, k)
-        if out is None:
-            out = torch.empty(n, dtype=buf.dtype, device=self.device)
-        elif out.dtype != buf.dtype or out.numel() != n or not out.is_contiguous():
-            raise ValueError(f"{what}: output must be a contiguous {buf.dtype} tensor of {n} elements")
-        _require_device(out, self.device, "output")
+        out = self._tiled_out(what, buf, n, out)
         nm = N.i64_array([n])
         need = int(self._lib.fa_weighted_sum_sqdist_scratch_bytes(1, nm, k))
         scratch = self._scratch("wsum_sqdist", need, stream)

@@ -115,10 +115,10 @@ def check_stats(stats, x, out, what):
         assert err.max() <= TOL, (what, name, float(err.max()))
 
 
-def run_flat(eng, x, sizes, offset, coef, what):
+def run_flat(eng, x, sizes, offset, coef, what, outs=None):
     from fedml_amd.engine import MUL_W
     segs = segments(x, sizes, offset)
-    outs, stats = eng.weighted_sum_sqdist(segs, coef)
+    outs, stats = eng.weighted_sum_sqdist(segs, coef, outs=outs)
     exp = eng.weighted_sum_multi(segs, MUL_W, coef)
     torch.cuda.synchronize()
     for s, (a, b) in enumerate(zip(outs, exp)):
@@ -147,6 +147,36 @@ def test_fused_pass_f32(eng, k):
 @pytest.mark.parametrize("dt", OTHER_DT, ids=str)
 def test_fused_pass_dtypes(eng, dt, k):
     _flat_cases(eng, k, dt, 200 + k)
+
+
+MIXED = [0, 5, 0, 4097]
+
+
+@pytest.mark.parametrize("offset", [0, 1], ids=["aligned", "offset1"])
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16], ids=str)
+def test_empty_segments_among_full_ones(eng, dt, offset):
+    """Empty segments before and between non-empty ones: the host path leaves them out of the
+    segment table, so the others' pointer-table base and first workgroup must count the kept segments
+    only -- here through the entry that appends its coefficients to the same staging slot.  The
+    outputs are views of one buffer of sentinels (each at a 16-byte boundary plus ``offset``
+    elements): the empty ones, and every element around the others, stay untouched."""
+    k = 3
+    g = torch.Generator().manual_seed(400 + offset)
+    x = normal_data(g, k, sum(MIXED), dt)
+    per16 = 16 // x.element_size()
+    starts, pos = [], per16
+    for n in MIXED:
+        starts.append(pos + offset)
+        pos += -(-(n + offset) // per16) * per16 + per16
+    guard = torch.full((pos,), 7.0, dtype=dt, device=DEV)
+    outs = [guard[s:s + n] for s, n in zip(starts, MIXED)]
+    out, _ = run_flat(eng, x, MIXED, offset, coefs(g, k), f"mixed k={k} {dt} offset={offset}", outs=outs)
+    keep = torch.ones(pos, dtype=torch.bool)
+    for s, n in zip(starts, MIXED):
+        keep[s:s + n] = False
+    got = guard.cpu()
+    assert bool((got[keep] == 7.0).all())
+    assert same_bits(got[~keep], out)  # the results are in the given outputs
 
 
 def tiled_buf(g, make, k, cap, n, dt):
