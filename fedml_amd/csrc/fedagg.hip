@@ -2072,14 +2072,15 @@ int mix_impl(fa_ctx* ctx, int dtype, int64_t n, int32_t rows, const int32_t* row
   bool aligned = true;
   for (int r = 0; r < rows; ++r) {
     if (row_ptr[r + 1] <= row_ptr[r]) return fail(FA_ERR_INVALID, "fa_mix: row %d is empty", r);
-    if (!d_out[r] || (post_scale && !d_out2[r])) return fail(FA_ERR_INVALID, "fa_mix: row %d output NULL", r);
+    // an empty tensor's data pointer is NULL: nothing is read or written when n == 0
+    if (n > 0 && (!d_out[r] || (post_scale && !d_out2[r]))) return fail(FA_ERR_INVALID, "fa_mix: row %d output NULL", r);
     aligned = aligned && al16(d_out[r]) && (!post_scale || al16(d_out2[r]));
   }
   const int32_t nnz = row_ptr[rows];
   for (int j = 0; j < nnz; ++j)
     if (cols[j] < 0 || cols[j] >= num_in) return fail(FA_ERR_INVALID, "fa_mix: col %d out of range", cols[j]);
   for (int i = 0; i < num_in; ++i) {
-    if (!d_in[i]) return fail(FA_ERR_INVALID, "fa_mix: input %d NULL", i);
+    if (n > 0 && !d_in[i]) return fail(FA_ERR_INVALID, "fa_mix: input %d NULL", i);
     aligned = aligned && al16(d_in[i]);
   }
   if (n == 0 && !dev_omega) return FA_OK;

@@ -632,7 +632,7 @@ class AggEngine:
             outs = [torch.empty(shape, dtype=dt, device=self.device) for _ in range(rows)]
         if post_scale is not None and outs2 is None:
             outs2 = [torch.empty(shape, dtype=dt, device=self.device) for _ in range(rows)]
-        in_set = {t.data_ptr() for t in xs}
+        in_set = {t.data_ptr() for t in xs if t.numel()}  # empty tensors share the NULL pointer
         for o in list(outs) + list(outs2 or []):
             _require_device(o, self.device, "mix output")
             if o.data_ptr() in in_set:
@@ -671,7 +671,7 @@ class AggEngine:
         elif omega_out.dtype != torch.float32 or omega_out.numel() != rows:
             raise ValueError("pushsum: omega_out must be float32 with one weight per row")
         _require_device(omega_out, self.device, "omega_out")
-        in_set = {t.data_ptr() for t in xs}
+        in_set = {t.data_ptr() for t in xs if t.numel()}  # empty tensors share the NULL pointer
         for o in outs + outs2:
             _require_device(o, self.device, "pushsum output")
             if o.data_ptr() in in_set:

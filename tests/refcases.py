@@ -233,3 +233,140 @@ def sa_order_and_flags(uploaded):
 def finite_case_inputs(meta, arrays):
     """(clients as int64/float CPU tensors per key) for a finite-field fixture."""
     return client_dicts(meta, arrays)
+
+
+# ----------------------------------------------------------------------------- mixing / gossip
+def oracle_pushsum(xs, row_ptr, cols, vals, omega_in, outs, outs2, omega_out):
+    """The engine's fa_pushsum restated: omega' = the row's ordered float32 chain, z = x' * fp32(1/omega')."""
+    from oracle import orc
+    om = omega_in.numpy().astype(np.float32)
+    new = []
+    for r in range(len(row_ptr) - 1):
+        acc = np.float32(-0.0)
+        for j in range(row_ptr[r], row_ptr[r + 1]):
+            acc = np.float32(acc + np.float32(om[cols[j]] * np.float32(vals[j])))
+        new.append(acc)
+    post = [float(np.float32(1.0) / a) for a in new]
+    o, o2 = orc.mix(xs, row_ptr, cols, vals, post_scale=post)
+    for a, b in zip(outs, o):
+        a.copy_(b)
+    for a, b in zip(outs2, o2):
+        a.copy_(b)
+    omega_out.copy_(torch.tensor([float(a) for a in new], dtype=torch.float32))
+
+
+MIX_SENTINEL = 7.0
+MIX_SPECIALS = [0.0, -0.0, float("inf"), float("-inf"), float("nan"), 1e-40, -6e-8, 65504.0]
+MIX_FINITE = [0.0, -0.0, 2.0, -3.0, 0.5, 1e-40, -6e-8, 65504.0]  # the same slots without inf / NaN
+MIX_INPUT0 = [-0.0, -0.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0]
+
+
+def mix_tile(dtype) -> int:
+    """Elements of one kernel tile (256 lanes x 16 bytes) = of one arena tile."""
+    return 256 * (16 // torch.empty(0, dtype=dtype).element_size())
+
+
+def mix_post_scale(rows: int):
+    return [1.0 / (1 + 0.25 * r) for r in range(rows)]
+
+
+def mix_inputs(dtype, num_in: int, n: int, seed: int, special: bool):
+    """num_in CPU vectors of randn * 2^randint(-12, 12); the first eight elements of every input are
+    the special values (``special``) or their finite stand-ins, input 0's are MIX_INPUT0.  The two
+    copies of one seed differ in those slots only."""
+    g = torch.Generator().manual_seed(seed)
+    head = MIX_SPECIALS if special else MIX_FINITE
+    xs = []
+    for i in range(num_in):
+        x = torch.randn(n, generator=g, dtype=torch.float64)
+        x = x * torch.pow(2.0, torch.randint(-12, 13, (n,), generator=g).double())
+        h = torch.tensor(MIX_INPUT0 if i == 0 else head, dtype=torch.float64)
+        x[:min(8, n)] = h[:min(8, n)]
+        xs.append(x.to(dtype))
+    return xs
+
+
+def torch_mix_reference(xs, row_ptr, cols, vals, post_scale=None):
+    """fa_mix per operation in plain torch: every product rounded to the dtype, every sum rounded to
+    the dtype, the first term passed through; weights and post-scales as float32."""
+    dt = xs[0].dtype
+    outs, outs2 = [], ([] if post_scale is not None else None)
+    for r in range(len(row_ptr) - 1):
+        acc = None
+        for j in range(row_ptr[r], row_ptr[r + 1]):
+            t = (xs[cols[j]].float() * torch.tensor(vals[j], dtype=torch.float64).float()).to(dt)
+            acc = t if acc is None else (acc.float() + t.float()).to(dt)
+        outs.append(acc)
+        if post_scale is not None:
+            outs2.append((acc.float() * torch.tensor(post_scale[r], dtype=torch.float64).float()).to(dt))
+    return outs, outs2
+
+
+def _normalised_rows(a: np.ndarray) -> np.ndarray:
+    a = a.astype(np.float32)
+    return a / a.sum(1, keepdims=True)
+
+
+def mix_matrices():
+    """name -> (row_ptr, cols, vals, num_in): the irregular gossip matrices of the mixing tests."""
+    import os
+    from fedml_amd.core.distributed.topology import topology_manager as tm
+    golden = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "topologies.npz"))
+    out = OrderedDict()
+
+    def add(name, csr, num_in):
+        out[name] = (list(csr[0]), list(csr[1]), list(csr[2]), num_in)
+
+    def ring(n):
+        m = tm.SymmetricTopologyManager(n, 2)
+        m.generate_topology()
+        return m.topology
+
+    for n in (3, 5, 8, 37):
+        add(f"ring{n}", tm.gossip_rows(ring(n)), n)
+    chain = np.eye(9) + np.eye(9, k=1) + np.eye(9, k=-1)
+    add("chain9", tm.gossip_rows(_normalised_rows(chain)), 9)
+    add("isolated9", tm.gossip_rows(tm.overlay_isolated(9)), 9)
+    add("star3", tm.gossip_rows(tm.overlay_star(3)), 3)
+    perm = np.random.RandomState(5).permutation(11)
+    add("ring11_permuted", tm.gossip_rows(ring(11)[np.ix_(perm, perm)]), 11)
+    add("balanced_tree7", tm.gossip_rows(tm.overlay_balanced_tree(7, 2)), 7)
+    for n in (7, 10):
+        a = np.eye(n)
+        for i in range(1, n):
+            a[i, (i - 1) // 2] = a[(i - 1) // 2, i] = 1
+        add(f"undirected_tree{n}", tm.gossip_rows(_normalised_rows(a)), n)
+    add("complete4_dense", tm.dense_rows(tm.overlay_complete(4)), 4)
+    add("star9", tm.gossip_rows(tm.overlay_star(9)), 9)
+    add("star12", tm.gossip_rows(tm.overlay_star(12)), 12)
+    add("torus9", tm.gossip_rows(tm.overlay_2d_torus(9)), 9)
+    add("random8", tm.gossip_rows(golden["W_random_8_seed3"]), 8)
+    add("random12", tm.gossip_rows(golden["W_random_12_seed4"]), 12)
+    add("complete11_dense", tm.dense_rows(tm.overlay_complete(11)), 11)
+    add("complete9_gossip", tm.gossip_rows(tm.overlay_complete(9)), 9)
+    hand = [[2, 0, 2, 1], [1], [0, 3, 3, 3, 3, 3, 3, 3, 3, 0]]
+    hvals = [[0.5, 0.0, -0.75, 0.1], [1.25], [0.1, 0.2, 0.0, -0.75, 0.1, 0.3, -0.05, 0.1, 0.25, 0.6]]
+    rp = [0]
+    for c in hand:
+        rp.append(rp[-1] + len(c))
+    add("handmade", (rp, sum(hand, []), sum(hvals, [])), 4)
+    return out
+
+
+def guarded_views(dtype, n: int, count: int, shifts=None, device="cuda:0"):
+    """``count`` views of n elements into one sentinel-filled buffer, each starting on a 16-byte
+    boundary plus shifts[i] elements, at least 16 bytes of sentinel on either side of every view.
+    Returns (buffer, views, starts)."""
+    vec = 16 // torch.empty(0, dtype=dtype).element_size()
+    slot = -(-n // vec) * vec + 2 * vec
+    buf = torch.full((count * slot + 2 * vec,), MIX_SENTINEL, dtype=dtype, device=device)
+    starts = [vec + i * slot + (shifts[i] if shifts else 0) for i in range(count)]
+    return buf, [buf[s:s + n] for s in starts], starts
+
+
+def guards_intact(buf, starts, n: int) -> bool:
+    """Every element of ``buf`` outside the views still holds the sentinel."""
+    outside = torch.ones(buf.numel(), dtype=torch.bool, device=buf.device)
+    for s in starts:
+        outside[s:s + n] = False
+    return bool((buf[outside] == MIX_SENTINEL).all())

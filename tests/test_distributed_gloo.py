@@ -13,6 +13,8 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+from refcases import oracle_pushsum as _oracle_pushsum  # shared with tests/test_gpu_mix.py
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -332,25 +334,6 @@ def test_reduce_scatter_out_untouched_gloo_world2():
 
 
 # ------------------------------------------------------------------------------ PushSum, device weights
-def _oracle_pushsum(xs, row_ptr, cols, vals, omega_in, outs, outs2, omega_out):
-    """The engine's fa_pushsum restated: omega' = the row's ordered float32 chain, z = x' * fp32(1/omega')."""
-    from oracle import orc
-    om = omega_in.numpy().astype(np.float32)
-    new = []
-    for r in range(len(row_ptr) - 1):
-        acc = np.float32(-0.0)
-        for j in range(row_ptr[r], row_ptr[r + 1]):
-            acc = np.float32(acc + np.float32(om[cols[j]] * np.float32(vals[j])))
-        new.append(acc)
-    post = [float(np.float32(1.0) / a) for a in new]
-    o, o2 = orc.mix(xs, row_ptr, cols, vals, post_scale=post)
-    for a, b in zip(outs, o):
-        a.copy_(b)
-    for a, b in zip(outs2, o2):
-        a.copy_(b)
-    omega_out.copy_(torch.tensor([float(a) for a in new], dtype=torch.float32))
-
-
 def _case_pushsum_device_omega(rank, world):
     from oracle import orc
     from fedml_amd.core.distributed.topology.topology_manager import SymmetricTopologyManager, gossip_rows
