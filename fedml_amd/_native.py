@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = (
     # include/fedagg_robust.h
     "fa_coord_median", "fa_coord_median_tiled", "fa_coord_trimmed_mean", "fa_coord_trimmed_mean_tiled",
     "fa_weighted_sum_sqdist", "fa_weighted_sum_sqdist_tiled", "fa_weighted_sum_sqdist_scratch_bytes", "fa_pairwise_sqdist", "fa_pairwise_sqdist_rt", "fa_pairwise_sqdist_scratch_bytes",
+    "fa_centered_sum_sqdist", "fa_centered_sum_sqdist_tiled",
     "fa_pairwise_sqdist_gram", "fa_pairwise_sqdist_gram_scratch_bytes", "fa_pairwise_sqdist_gram_limit",
     # include/fedagg_comm.h
     "fa_comm_unique_id", "fa_comm_init", "fa_comm_wrap", "fa_comm_destroy", "fa_comm_size", "fa_local_out_dtype",
@@ -176,6 +177,12 @@ def _declare(L):
     L.fa_weighted_sum_sqdist_tiled.restype = ctypes.c_int
     L.fa_weighted_sum_sqdist_tiled.argtypes = [_vp, ctypes.c_int, ctypes.c_int32, _P_i64, ctypes.c_int32, _P_vp,
                                                ctypes.c_int64, _P_d, _P_vp, _vp, _vp, ctypes.c_size_t, _vp]
+    L.fa_centered_sum_sqdist.restype = ctypes.c_int
+    L.fa_centered_sum_sqdist.argtypes = [_vp, ctypes.c_int, ctypes.c_int32, _P_i64, ctypes.c_int32, _P_vp, _P_vp, _P_d,
+                                         _P_vp, _vp, _vp, ctypes.c_size_t, _vp]
+    L.fa_centered_sum_sqdist_tiled.restype = ctypes.c_int
+    L.fa_centered_sum_sqdist_tiled.argtypes = [_vp, ctypes.c_int, ctypes.c_int32, _P_i64, ctypes.c_int32, _P_vp,
+                                               ctypes.c_int64, _P_vp, _P_d, _P_vp, _vp, _vp, ctypes.c_size_t, _vp]
     L.fa_weighted_sum_sqdist_scratch_bytes.restype = ctypes.c_size_t
     L.fa_weighted_sum_sqdist_scratch_bytes.argtypes = [ctypes.c_int32, _P_i64, ctypes.c_int32]
     L.fa_pairwise_sqdist.restype = ctypes.c_int

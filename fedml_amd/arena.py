@@ -39,6 +39,7 @@ import torch
 
 from . import _host
 from .engine import MUL_N_DIV_N, MUL_W, SUM, AggEngine, get_engine, out_dtype
+from .cclip import cclip_driver
 from .weiszfeld import weiszfeld_driver
 
 _ALIGN_ELEMS = 64
@@ -568,6 +569,74 @@ class ClientArena:
             return sum_stats(stats)
 
         res = weiszfeld_driver(counts, iters, nu, step)
+        if info is not None:
+            info.update(res)
+        return self.layout.carve(outs)
+
+    def centered_clip(self, counts: Sequence[float], tau: float, iters: int = 1,
+                      center: Optional[Dict[torch.dtype, torch.Tensor]] = None,
+                      clients: Optional[Sequence[int]] = None,
+                      out: Optional[Dict[torch.dtype, torch.Tensor]] = None,
+                      info: Optional[dict] = None) -> "OrderedDict[str, torch.Tensor]":
+        """Centered clipping (Karimireddy, He, Jaggi 2021; fedml_amd/cclip.py) of the given client rows
+        (default: all) weighted by ``counts`` (aligned with ``clients``): ``iters`` iterations
+        v <- v + sum_i s_i (x_i - v) with radius ``tau`` from ``center`` (dtype -> flat device tensor of
+        the group's elements in the layout's order; modified only where it is ``out`` itself), each ONE in-place
+        fa_centered_sum_sqdist launch per dtype group whose distances serve the next iteration, after
+        one distance-only launch for the distances to the center.  ``center`` None: the start is the
+        sample-weighted mean and pass 0 the fa_weighted_sum_sqdist launch that forms it.  Tiled arenas
+        go through the tiled entries, client-major arenas over the row views; with several dtype
+        groups the distances are added across groups on the host in the order of ``self.bufs``.  Rows
+        holding a NaN or Inf are dropped (``info["dropped"]``, positions in ``clients``).  Float groups
+        only.  ``info`` (optional dict) receives the driver's traces.  Returns per-key views of the
+        last iterate (the start point when ``iters`` is 0)."""
+        rows = list(range(self.capacity)) if clients is None else list(clients)
+        if not rows:
+            raise ValueError("centered_clipping: no client rows")
+        if len(counts) != len(rows):
+            raise ValueError("centered_clipping: need one count per client row")
+        if any(dt not in (torch.float32, torch.bfloat16, torch.float16, torch.float64) for dt in self.bufs):
+            raise TypeError("centered_clipping: the arena holds a non-float dtype group")
+        if center is not None:
+            for dt in self.bufs:
+                c = center.get(dt)
+                n = self.layout.group_numel[dt]
+                if c is None or c.dtype != dt or c.numel() != n or not c.is_contiguous():
+                    raise ValueError(f"centered_clipping: center[{dt}] must be a contiguous {dt} tensor of {n} "
+                                     f"elements")
+        self._wait_ingest()
+        eng = self.engine
+        outs: Dict[torch.dtype, torch.Tensor] = {}
+        for dt, buf in self.bufs.items():
+            o = out[dt] if out is not None else None
+            outs[dt] = o if o is not None else torch.empty(self.layout.group_numel[dt], dtype=dt, device=buf.device)
+
+        def run(idx, coef, centered):
+            # one launch per dtype group, v = outs[dt] in place: the mean and the distances to it
+            # (not centered), the distances to v (coef None), or one clipping step
+            sel = [rows[j] for j in idx]
+            stats = []
+            for dt, buf in self.bufs.items():
+                n, v = self.layout.group_numel[dt], outs[dt]
+                if self.tiled:
+                    stats.append(eng.centered_sum_sqdist_tiled(buf, sel, v.reshape(-1), coef, n=n, out=v)[1] if centered
+                                 else eng.weighted_sum_sqdist_tiled(buf, sel, coef, n=n, out=v)[1])
+                else:
+                    segs = [[buf[i][:n] for i in sel]]
+                    stats.append(eng.centered_sum_sqdist(segs, [v.reshape(-1)], coef, outs=[v])[1] if centered
+                                 else eng.weighted_sum_sqdist(segs, coef, outs=[v])[1])
+            return sum_stats(stats)
+
+        def first(idx):
+            if center is None:
+                tot = sum(float(counts[j]) for j in idx)
+                return run(idx, [float(counts[j]) / tot for j in idx], False)
+            for dt in self.bufs:
+                if outs[dt].data_ptr() != center[dt].data_ptr():
+                    outs[dt].reshape(-1).copy_(center[dt].reshape(-1))
+            return run(idx, None, True)
+
+        res = cclip_driver(counts, iters, tau, first, lambda scales, idx: run(idx, scales, True))
         if info is not None:
             info.update(res)
         return self.layout.carve(outs)

@@ -3,7 +3,10 @@ robust aggregators of this engine: krum / multikrum, trimmed_mean, wise_median,
 coordinate_trimmed_mean (the per-coordinate trimmed mean of Yin et al. 2018, which the reference
 lacks: its trimmed_mean trims whole clients and keeps that meaning here) and geometric_median (the
 sample-weighted geometric median by the smoothed Weiszfeld iteration of Pillutla et al.; config
-geomed_iters, geomed_nu; the reference's own RFA name stays unserved).  Same dispatch
+geomed_iters, geomed_nu; the reference's own RFA name stays unserved) and centered_clipping (centered
+clipping of Karimireddy et al. around the global model or the mean, one iteration of which is
+norm-difference clipping followed by FedAvg; config cclip_tau, cclip_iters, cclip_center; the
+reference's cclip and norm_diff_clipping names stay unserved).  Same dispatch
 (which defenses act before / on / after aggregation) and the same entry points; the per-element work
 runs in the HIP kernels (fedml_amd/csrc/median.hip, trimmed.hip, wsum_dist.hip, robust.hip).  Other
 defense types of the reference are outside the aggregation path and raise NotImplementedError when
@@ -15,8 +18,9 @@ import logging
 from collections import OrderedDict
 from typing import Any, Callable, List, Tuple
 
-from .constants import (DEFENSE_COORD_TRIMMED_MEAN, DEFENSE_GEOMETRIC_MEDIAN, DEFENSE_KRUM, DEFENSE_MULTIKRUM,
-                        DEFENSE_TRIMMED_MEAN, DEFENSE_WISE_MEDIAN)
+from .constants import (DEFENSE_CENTERED_CLIPPING, DEFENSE_COORD_TRIMMED_MEAN, DEFENSE_GEOMETRIC_MEDIAN, DEFENSE_KRUM,
+                        DEFENSE_MULTIKRUM, DEFENSE_TRIMMED_MEAN, DEFENSE_WISE_MEDIAN)
+from .defense.centered_clipping_defense import CenteredClippingDefense
 from .defense.coordinate_trimmed_mean_defense import CoordinateTrimmedMeanDefense
 from .defense.coordinate_wise_median_defense import CoordinateWiseMedianDefense
 from .defense.coordinate_wise_trimmed_mean_defense import CoordinateWiseTrimmedMeanDefense
@@ -54,11 +58,13 @@ class FedMLDefender:
                 self.defender = CoordinateTrimmedMeanDefense(args)
             elif self.defense_type == DEFENSE_GEOMETRIC_MEDIAN:
                 self.defender = GeometricMedianDefense(args)
+            elif self.defense_type == DEFENSE_CENTERED_CLIPPING:
+                self.defender = CenteredClippingDefense(args)
             else:
                 raise NotImplementedError(
                     f"defense_type {self.defense_type!r} is not served by the MI355X engine "
                     f"(supported: krum, multikrum, trimmed_mean, wise_median, coordinate_trimmed_mean, "
-                    f"geometric_median)")
+                    f"geometric_median, centered_clipping)")
         else:
             self.is_enabled = False
             self.defense_type = None
@@ -70,7 +76,8 @@ class FedMLDefender:
     def is_defense_on_aggregation(self):
         return self.is_defense_enabled() and self.defense_type in [DEFENSE_WISE_MEDIAN,
                                                                                DEFENSE_COORD_TRIMMED_MEAN,
-                                                                               DEFENSE_GEOMETRIC_MEDIAN]
+                                                                               DEFENSE_GEOMETRIC_MEDIAN,
+                                                                               DEFENSE_CENTERED_CLIPPING]
 
     def is_defense_before_aggregation(self):
         return self.is_defense_enabled() and self.defense_type in [DEFENSE_KRUM, DEFENSE_MULTIKRUM,

@@ -2,7 +2,7 @@
 // trimmed.hip, wsum_dist.hip): argument checks, the grid for a given element count per workgroup,
 // the MSeg + pointer table (and an entry's own payload) in a staging slot, and the launch.  An entry
 // checks in this order: col_check_args (NULL context, then the other arguments), its own arguments
-// (the trim; coef and d_stats), col_count (dtype, tile_stride, then the segments), its scratch.
+// (the trim; d_center, coef and d_stats), col_count (dtype, tile_stride, then the segments), its scratch.
 // Not part of the ABI.
 #pragma once
 
@@ -23,6 +23,10 @@ struct ColArgs {
   int64_t tstride;          // 0: flat segments; > 0: tile-interleaved inputs
   void* const* d_out;
   void* hip_stream;
+  // wsum_dist.hip's centered entries: [num_segments] flat tensors, checked with the segments and
+  // part of a segment's `aligned`; the entry stages the pointers in its own payload, so the
+  // tables staged here do not depend on them.  NULL: no center.
+  const void* const* d_center = nullptr;
 };
 
 inline int col_check_args(const ColArgs& a) {
@@ -47,6 +51,7 @@ static inline int col_count(const ColArgs& a, int64_t cols, int* nseg, int64_t* 
   for (int s = 0; s < a.num_segments; ++s) {
     if (a.seg_numel[s] < 0) return fail(FA_ERR_INVALID, "%s: segment %d has negative numel", a.fn, s);
     if (a.seg_numel[s] == 0) continue;
+    if (a.d_center && !a.d_center[s]) return fail(FA_ERR_INVALID, "%s: segment %d: center NULL", a.fn, s);
     if (!a.d_out[s]) return fail(FA_ERR_INVALID, "%s: segment %d: output NULL", a.fn, s);
     for (int i = 0; i < a.k; ++i)
       if (!a.d_in[(int64_t)s * a.k + i])
@@ -82,7 +87,7 @@ int col_stage_launch(const ColArgs& a, int64_t cols, int nseg, int64_t tiles, si
   for (int s = 0; s < a.num_segments; ++s) {
     const int64_t n = a.seg_numel[s];
     if (n == 0) continue;
-    bool aligned = al16(a.d_out[s]);
+    bool aligned = al16(a.d_out[s]) && (!a.d_center || al16(a.d_center[s]));
     for (int i = 0; i < k; ++i) {
       hp[(int64_t)j * k + i] = a.d_in[(int64_t)s * k + i];
       aligned = aligned && al16(a.d_in[(int64_t)s * k + i]);

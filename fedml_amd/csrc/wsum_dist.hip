@@ -21,6 +21,12 @@
 // registers between the phases and reads the input once.  k_wsd_reduce then adds the rows in a fixed
 // order (k_gram_reduce's split, robust.hip): no floating-point atomics anywhere, so the same call
 // gives the same bits.  Kept and lost forms, with their numbers: DESIGN.md.
+//
+// fa_centered_sum_sqdist[_tiled] (one pass of centered clipping) are the same kernels in two more
+// modes of the template parameter CM: kCenter forms out = op(center + the ordered sum of
+// t_i = op(op(x_i - center) c_i)) around a flat center the caller supplies and measures against that
+// out; kDist (coef NULL) measures against the center itself in one walk and stores nothing.  The
+// center pointers travel in the entry's payload behind the coefficients.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -51,6 +57,7 @@ __device__ __forceinline__ void st1(void* p, int64_t e, typename El<DT>::A v) {
 constexpr int kS = 4;     // 4-KiB slots per client and workgroup
 constexpr int kKB = 128;  // clients per pass of phase 2 (the LDS block of wave sums)
 constexpr int kRows = kBlock / 16;  // 16-lane DPP rows per workgroup
+enum { kPlain = 0, kCenter = 1, kDist = 2 };  // what a pass forms (wsd_chunk)
 
 // Sum over the lane's 16-lane row, left in every lane of the row: four DPP exchanges (xor 1, xor 2 by
 // quad_perm, then row_half_mirror and row_mirror), plain VALU, in a fixed order.  The rows of a wave
@@ -121,10 +128,22 @@ struct Chunk {
   }
 };
 
-template <int DT, bool VEC>
+// The element's term of client i.  CM == kPlain: t_i = op(x_i c_i); kCenter: u_i = op(x_i - center),
+// t_i = op(u_i c_i).
+template <int DT, int CM>
+__device__ __forceinline__ typename El<DT>::A wsd_term(typename El<DT>::A x, typename El<DT>::A cen,
+                                                       typename El<DT>::A c) {
+  using T = El<DT>;
+  if constexpr (CM == kCenter) return T::rnd(op_mul(T::rnd(op_sub(x, cen)), c));
+  else return T::rnd(op_mul(x, c));
+}
+
+// CM: kPlain, the weighted sum; kCenter, out = op(center + the ordered sum of the clipped differences);
+// kDist, out IS the center: no first walk and no store.  `center`: the segment's flat center (CM != kPlain).
+template <int DT, bool VEC, int CM>
 __device__ __forceinline__ void wsd_chunk(const MSeg& sg, int64_t tl, const void* const* __restrict__ in,
-                                          const double* __restrict__ coef, int k, double* __restrict__ part,
-                                          double (&red)[kRows][2 * kKB]) {
+                                          const void* __restrict__ center, const double* __restrict__ coef, int k,
+                                          double* __restrict__ part, double (&red)[kRows][2 * kKB]) {
   using C = Chunk<DT, VEC>;
   using T = El<DT>;
   using A = typename T::A;
@@ -154,11 +173,31 @@ __device__ __forceinline__ void wsd_chunk(const MSeg& sg, int64_t tl, const void
     }
   }
 
+  // the lane's elements of the center (flat, like out; the lane that owns an element reads it here
+  // and only then stores it, so out may be the center itself)
+  A cen[CM == kPlain ? 1 : NE] = {};
+  if constexpr (CM != kPlain) {
+    if constexpr (VEC) {
+#pragma unroll
+      for (int s = 0; s < kS; ++s)
+        T::unpack(*(const __attribute__((address_space(1))) u32x4*)((const char*)center + (e0 + s * E) * T::SZ +
+                                                                     (int64_t)tid * 16),
+                  &cen[s * V]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < NE; ++j) {
+        const int64_t e = e0 + (int64_t)j * kBlock + tid;
+        cen[j] = ld1<DT>(center, e < sg.numel ? e : sg.numel - 1);
+      }
+    }
+  }
+
   // phase 1: out, clients in order
   A acc[NE];
 #pragma unroll
-  for (int j = 0; j < NE; ++j) acc[j] = (A)-0.0;  // -0 + t == t bitwise for every t
-  {
+  for (int j = 0; j < NE; ++j)
+    acc[j] = CM == kDist ? cen[CM == kPlain ? 0 : j] : (A)-0.0;  // -0 + t == t bitwise for every t
+  if constexpr (CM != kDist) {
     int i0 = 0;
     for (; i0 + U <= k; i0 += U) {
       typename C::Raw r[U][NR];
@@ -170,7 +209,8 @@ __device__ __forceinline__ void wsd_chunk(const MSeg& sg, int64_t tl, const void
         A x[NE];
         C::get(r[u], x);
 #pragma unroll
-        for (int j = 0; j < NE; ++j) acc[j] = T::rnd(op_add(acc[j], T::rnd(op_mul(x[j], c))));
+        for (int j = 0; j < NE; ++j)
+          acc[j] = T::rnd(op_add(acc[j], wsd_term<DT, CM>(x[j], cen[CM == kPlain ? 0 : j], c)));
       }
     }
     if (i0 < k) {
@@ -184,19 +224,24 @@ __device__ __forceinline__ void wsd_chunk(const MSeg& sg, int64_t tl, const void
           A x[NE];
           C::get(r[u], x);
 #pragma unroll
-          for (int j = 0; j < NE; ++j) acc[j] = T::rnd(op_add(acc[j], T::rnd(op_mul(x[j], c))));
+          for (int j = 0; j < NE; ++j)
+            acc[j] = T::rnd(op_add(acc[j], wsd_term<DT, CM>(x[j], cen[CM == kPlain ? 0 : j], c)));
         }
       }
     }
-  }
-  if constexpr (VEC) {
+    if constexpr (CM == kCenter) {
 #pragma unroll
-    for (int s = 0; s < kS; ++s)
-      *(u32x4*)((char*)sg.out + (e0 + s * E) * T::SZ + (int64_t)tid * 16) = T::pack(&acc[s * V]);
-  } else {
+      for (int j = 0; j < NE; ++j) acc[j] = T::rnd(op_add(cen[j], acc[j]));
+    }
+    if constexpr (VEC) {
 #pragma unroll
-    for (int j = 0; j < NE; ++j)
-      if (live >> j & 1u) st1<DT>(sg.out, e0 + (int64_t)j * kBlock + tid, acc[j]);
+      for (int s = 0; s < kS; ++s)
+        *(u32x4*)((char*)sg.out + (e0 + s * E) * T::SZ + (int64_t)tid * 16) = T::pack(&acc[s * V]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < NE; ++j)
+        if (live >> j & 1u) st1<DT>(sg.out, e0 + (int64_t)j * kBlock + tid, acc[j]);
+    }
   }
 
   // phase 2: the two sums of every client against the registers' out, kKB clients per LDS block
@@ -234,21 +279,24 @@ __device__ __forceinline__ void wsd_chunk(const MSeg& sg, int64_t tl, const void
   }
 }
 
-template <int DT>
+// cens[j]: the center of the table's segment j (CM != kPlain; not read otherwise)
+template <int DT, int CM>
 __global__ void __launch_bounds__(kBlock)
 k_wsd(const MSeg* __restrict__ segs, int nseg, const void* const* __restrict__ ptrs,
-      const double* __restrict__ coef, int k, double* __restrict__ partial) {
+      const void* const* __restrict__ cens, const double* __restrict__ coef, int k, double* __restrict__ partial) {
   __shared__ double red[kRows][2 * kKB];
   constexpr int64_t CH = kS * (FA_TILE_BYTES / El<DT>::SZ);  // elements per chunk
   const int64_t tile = blockIdx.x;
-  const MSeg sg = segs[nseg > 1 ? find_seg(segs, nseg, tile) : 0];
+  const int si = nseg > 1 ? find_seg(segs, nseg, tile) : 0;
+  const MSeg sg = segs[si];
   const int64_t tl = tile - sg.tile_start;
   const void* const* in = ptrs + sg.ptr_base;
+  const void* center = CM == kPlain ? nullptr : cens[si];
   double* part = partial + tile * (2 * (int64_t)k);
   if (sg.aligned && (tl + 1) * CH <= sg.numel)
-    wsd_chunk<DT, true>(sg, tl, in, coef, k, part, red);
+    wsd_chunk<DT, true, CM>(sg, tl, in, center, coef, k, part, red);
   else
-    wsd_chunk<DT, false>(sg, tl, in, coef, k, part, red);
+    wsd_chunk<DT, false, CM>(sg, tl, in, center, coef, k, part, red);
 }
 
 // Single-read form, K <= KM <= 32: the same chunk, one 4-KiB slot at a time with the slot's K x 16
@@ -259,22 +307,26 @@ k_wsd(const MSeg* __restrict__ segs, int nseg, const void* const* __restrict__ p
 // every load of a slot is issued before the first is consumed.  The row leaders keep their running
 // sums over the four slots in LDS; the sums' order differs from the generic kernel's, the bound does
 // not.  Chunks that are ragged or unaligned take the generic element-load path.
-template <int DT, int KM>
+// The centered forms hold the slot's 16 bytes of the center beside the K rows.
+template <int DT, int KM, int CM>
 __global__ void __launch_bounds__(kBlock)
 k_wsd_reg(const MSeg* __restrict__ segs, int nseg, const void* const* __restrict__ ptrs,
-          const double* __restrict__ coef, int k, double* __restrict__ partial) {
+          const void* const* __restrict__ cens, const double* __restrict__ coef, int k,
+          double* __restrict__ partial) {
   using T = El<DT>;
   using A = typename T::A;
   constexpr int V = T::V;
   constexpr int64_t E = FA_TILE_BYTES / T::SZ, CH = kS * E;
   __shared__ double red[kRows][2 * kKB];
   const int64_t tile = blockIdx.x;
-  const MSeg sg = segs[nseg > 1 ? find_seg(segs, nseg, tile) : 0];
+  const int si = nseg > 1 ? find_seg(segs, nseg, tile) : 0;
+  const MSeg sg = segs[si];
   const int64_t tl = tile - sg.tile_start;
   const void* const* in = ptrs + sg.ptr_base;
+  const void* center = CM == kPlain ? nullptr : cens[si];
   double* part = partial + tile * (2 * (int64_t)k);
   if (!(sg.aligned && (tl + 1) * CH <= sg.numel)) {
-    wsd_chunk<DT, false>(sg, tl, in, coef, k, part, red);
+    wsd_chunk<DT, false, CM>(sg, tl, in, center, coef, k, part, red);
     return;
   }
   const int tid = (int)threadIdx.x, row = tid >> 4;
@@ -288,21 +340,31 @@ k_wsd_reg(const MSeg* __restrict__ segs, int nseg, const void* const* __restrict
     for (int i = 0; i < KM; ++i)
       r[i] = __builtin_nontemporal_load(
           (const __attribute__((address_space(1))) u32x4*)((const char*)in[min(i, k - 1)] + off));
+    A cen[V] = {};  // read by the lane that stores these 16 bytes of out below: out may be the center
+    if constexpr (CM != kPlain)
+      T::unpack(*(const __attribute__((address_space(1))) u32x4*)((const char*)center + es * T::SZ + (int64_t)tid * 16),
+                cen);
     A acc[V];
 #pragma unroll
-    for (int v = 0; v < V; ++v) acc[v] = (A)-0.0;
+    for (int v = 0; v < V; ++v) acc[v] = CM == kDist ? cen[v] : (A)-0.0;
+    if constexpr (CM != kDist) {
 #pragma unroll
-    for (int i = 0; i < KM; ++i) {
-      const A c = (A)coef[min(i, k - 1)];
-      A x[V];
-      T::unpack(r[i], x);
+      for (int i = 0; i < KM; ++i) {
+        const A c = (A)coef[min(i, k - 1)];
+        A x[V];
+        T::unpack(r[i], x);
 #pragma unroll
-      for (int v = 0; v < V; ++v) {
-        const A nxt = T::rnd(op_add(acc[v], T::rnd(op_mul(x[v], c))));
-        acc[v] = i < k ? nxt : acc[v];
+        for (int v = 0; v < V; ++v) {
+          const A nxt = T::rnd(op_add(acc[v], wsd_term<DT, CM>(x[v], cen[v], c)));
+          acc[v] = i < k ? nxt : acc[v];
+        }
       }
+      if constexpr (CM == kCenter) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) acc[v] = T::rnd(op_add(cen[v], acc[v]));
+      }
+      *(u32x4*)((char*)sg.out + es * T::SZ + (int64_t)tid * 16) = T::pack(acc);
     }
-    *(u32x4*)((char*)sg.out + es * T::SZ + (int64_t)tid * 16) = T::pack(acc);
 #pragma unroll
     for (int i = 0; i < KM; ++i) {
       A x[V];
@@ -367,10 +429,38 @@ int64_t chunk_elems(int dtype) {
   return (int64_t)kS * (FA_TILE_BYTES / (dtype == FA_DTYPE_F64 ? 8 : dtype == FA_DTYPE_F32 ? 4 : 2));
 }
 
-int wsd_impl(const ColArgs& a, const double* coef, void* d_stats, void* d_scratch, size_t scratch_bytes) {
+// The launch of one pass in mode CM (the kernels' template parameter).
+template <int CM>
+void wsd_launch(int dtype, int k, dim3 grid, hipStream_t st, const MSeg* ds, int n, const void* const* dp,
+                const void* const* dcen, const double* dc, double* part) {
+  const dim3 block(kBlock);
+  if (dtype == FA_DTYPE_F32 && k <= kRegMaxK && wsd_reg_enabled()) {
+    switch ((k + 7) / 8) {  // KM = K rounded up to 8
+#define FA_WR(Q) \
+  case Q: hipLaunchKernelGGL((k_wsd_reg<FA_DTYPE_F32, 8 * Q, CM>), grid, block, 0, st, ds, n, dp, dcen, dc, k, part); break;
+      FA_WR(1) FA_WR(2) FA_WR(3) FA_WR(4)
+#undef FA_WR
+    }
+    return;
+  }
+  switch (dtype) {
+#define FA_WG(DT) \
+  case DT: hipLaunchKernelGGL((k_wsd<DT, CM>), grid, block, 0, st, ds, n, dp, dcen, dc, k, part); break;
+    FA_WG(FA_DTYPE_F32) FA_WG(FA_DTYPE_BF16) FA_WG(FA_DTYPE_F16)
+    default: hipLaunchKernelGGL((k_wsd<FA_DTYPE_F64, CM>), grid, block, 0, st, ds, n, dp, dcen, dc, k, part); break;
+#undef FA_WG
+  }
+}
+
+// centered: the fa_centered_* entries (a.d_center is theirs; coef NULL: distance-only, d_out unused).
+int wsd_impl(ColArgs a, bool centered, const double* coef, void* d_stats, void* d_scratch, size_t scratch_bytes) {
+  const void* const* d_center = a.d_center;
+  const int mode = !centered ? kPlain : coef ? kCenter : kDist;
+  if (mode == kDist) a.d_out = (void* const*)d_center;  // nothing is stored: the table's out is the center
   if (const int rc = col_check_args(a)) return rc;
   const int k = a.k;
-  if (!coef) return fail(FA_ERR_INVALID, "%s: coef is NULL", a.fn);
+  if (centered && !d_center) return fail(FA_ERR_INVALID, "%s: d_center is NULL", a.fn);
+  if (!centered && !coef) return fail(FA_ERR_INVALID, "%s: coef is NULL", a.fn);
   if (!d_stats) return fail(FA_ERR_INVALID, "%s: d_stats is NULL", a.fn);
   const int64_t ch = chunk_elems(a.dtype);
   int nseg;
@@ -387,28 +477,25 @@ int wsd_impl(const ColArgs& a, const double* coef, void* d_stats, void* d_scratc
     return FA_OK;
   }
   double* part = (double*)d_scratch;
+  // the payload: the k coefficients, then (centered) the non-empty segments' center pointers
+  const size_t coef_bytes = sizeof(double) * (size_t)k;
   return col_stage_launch(
-      a, ch, nseg, tiles, sizeof(double) * (size_t)k,
+      a, ch, nseg, tiles, coef_bytes + (centered ? sizeof(void*) * (size_t)nseg : 0),
       [&](void* h) {
-        for (int i = 0; i < k; ++i) ((double*)h)[i] = coef[i];
+        for (int i = 0; i < k; ++i) ((double*)h)[i] = coef ? coef[i] : 0.0;
+        if (centered) {
+          const void** hc = (const void**)((char*)h + coef_bytes);
+          for (int s = 0, j = 0; s < a.num_segments; ++s)
+            if (a.seg_numel[s]) hc[j++] = d_center[s];
+        }
       },
       [&](dim3 grid, hipStream_t st, const MSeg* ds, int n, const void* const* dp, const void* payload) {
         const double* dc = (const double*)payload;
-        const dim3 block(kBlock);
-        if (a.dtype == FA_DTYPE_F32 && k <= kRegMaxK && wsd_reg_enabled()) {
-          switch ((k + 7) / 8) {  // KM = K rounded up to 8
-#define FA_WR(Q) \
-  case Q: hipLaunchKernelGGL((k_wsd_reg<FA_DTYPE_F32, 8 * Q>), grid, block, 0, st, ds, n, dp, dc, k, part); break;
-            FA_WR(1) FA_WR(2) FA_WR(3) FA_WR(4)
-#undef FA_WR
-          }
-        } else {
-          switch (a.dtype) {
-            case FA_DTYPE_F32: hipLaunchKernelGGL((k_wsd<FA_DTYPE_F32>), grid, block, 0, st, ds, n, dp, dc, k, part); break;
-            case FA_DTYPE_BF16: hipLaunchKernelGGL((k_wsd<FA_DTYPE_BF16>), grid, block, 0, st, ds, n, dp, dc, k, part); break;
-            case FA_DTYPE_F16: hipLaunchKernelGGL((k_wsd<FA_DTYPE_F16>), grid, block, 0, st, ds, n, dp, dc, k, part); break;
-            default: hipLaunchKernelGGL((k_wsd<FA_DTYPE_F64>), grid, block, 0, st, ds, n, dp, dc, k, part); break;
-          }
+        const void* const* dcen = (const void* const*)((const char*)payload + coef_bytes);
+        switch (mode) {
+          case kPlain: wsd_launch<kPlain>(a.dtype, k, grid, st, ds, n, dp, nullptr, dc, part); break;
+          case kCenter: wsd_launch<kCenter>(a.dtype, k, grid, st, ds, n, dp, dcen, dc, part); break;
+          default: wsd_launch<kDist>(a.dtype, k, grid, st, ds, n, dp, dcen, dc, part); break;
         }
         hipLaunchKernelGGL(k_wsd_reduce, dim3((unsigned)((2 * k + kRE - 1) / kRE)), dim3(64 * kRW), 0, st,
                            (const double*)part, tiles, 2 * k, (double*)d_stats);
@@ -422,8 +509,8 @@ extern "C" {
 int fa_weighted_sum_sqdist(fa_ctx* ctx, int dtype, int32_t num_segments, const int64_t* seg_numel, int32_t k,
                            const void* const* d_in, const double* coef, void* const* d_out, void* d_stats,
                            void* d_scratch, size_t scratch_bytes, void* hip_stream) {
-  return wsd_impl({"fa_weighted_sum_sqdist", ctx, dtype, num_segments, seg_numel, k, d_in, 0, d_out, hip_stream}, coef,
-                  d_stats, d_scratch, scratch_bytes);
+  return wsd_impl({"fa_weighted_sum_sqdist", ctx, dtype, num_segments, seg_numel, k, d_in, 0, d_out, hip_stream}, false,
+                  coef, d_stats, d_scratch, scratch_bytes);
 }
 
 int fa_weighted_sum_sqdist_tiled(fa_ctx* ctx, int dtype, int32_t num_segments, const int64_t* seg_numel, int32_t k,
@@ -432,7 +519,25 @@ int fa_weighted_sum_sqdist_tiled(fa_ctx* ctx, int dtype, int32_t num_segments, c
   if (ctx && tile_stride <= 0) return fail(FA_ERR_INVALID, "fa_weighted_sum_sqdist_tiled: tile_stride must be > 0");
   return wsd_impl({"fa_weighted_sum_sqdist_tiled", ctx, dtype, num_segments, seg_numel, k, d_in, tile_stride, d_out,
                    hip_stream},
-                  coef, d_stats, d_scratch, scratch_bytes);
+                  false, coef, d_stats, d_scratch, scratch_bytes);
+}
+
+int fa_centered_sum_sqdist(fa_ctx* ctx, int dtype, int32_t num_segments, const int64_t* seg_numel, int32_t k,
+                           const void* const* d_in, const void* const* d_center, const double* coef,
+                           void* const* d_out, void* d_stats, void* d_scratch, size_t scratch_bytes, void* hip_stream) {
+  return wsd_impl({"fa_centered_sum_sqdist", ctx, dtype, num_segments, seg_numel, k, d_in, 0, d_out, hip_stream,
+                   d_center},
+                  true, coef, d_stats, d_scratch, scratch_bytes);
+}
+
+int fa_centered_sum_sqdist_tiled(fa_ctx* ctx, int dtype, int32_t num_segments, const int64_t* seg_numel, int32_t k,
+                                 const void* const* d_in, int64_t tile_stride, const void* const* d_center,
+                                 const double* coef, void* const* d_out, void* d_stats, void* d_scratch,
+                                 size_t scratch_bytes, void* hip_stream) {
+  if (ctx && tile_stride <= 0) return fail(FA_ERR_INVALID, "fa_centered_sum_sqdist_tiled: tile_stride must be > 0");
+  return wsd_impl({"fa_centered_sum_sqdist_tiled", ctx, dtype, num_segments, seg_numel, k, d_in, tile_stride, d_out,
+                   hip_stream, d_center},
+                  true, coef, d_stats, d_scratch, scratch_bytes);
 }
 
 // The per-chunk rows of the smallest chunk any dtype uses (float64's), so one size serves every dtype.

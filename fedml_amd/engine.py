@@ -1009,6 +1009,74 @@ class AggEngine:
         N.check(rc, "fa_weighted_sum_sqdist_tiled")
         return out, stats
 
+    def _check_center(self, what: str, c: torch.Tensor, dt, n: int, where: str) -> None:
+        if c.dtype != dt or c.numel() != n or not c.is_contiguous():
+            raise ValueError(f"{what}: {where} must be a contiguous {dt} tensor of {n} elements")
+        _require_device(c, self.device, where)
+
+    def centered_sum_sqdist(self, segments: Sequence[Sequence[torch.Tensor]], centers: Sequence[torch.Tensor],
+                            coef: Optional[Sequence[float]], outs: Optional[Sequence[torch.Tensor]] = None,
+                            stream=None) -> Tuple[Optional[List[torch.Tensor]], torch.Tensor]:
+        """One pass of centered clipping (fa_centered_sum_sqdist): out = center + the ordered sum of
+        coef_i (x_i - center), every difference rounded in the dtype, and ``stats`` = a [2, K] float64
+        device tensor: stats[0, i] = sum over all segments of (x_i - out)^2 against the stored out,
+        stats[1, i] = sum of x_i^2 (include/fedagg_robust.h).  centers[s]: segment s's center, the
+        segment's dtype and element count; outs[s] may be centers[s] itself (in place).  ``coef`` None:
+        distance-only -- stats[0, i] = sum of (x_i - center)^2, nothing else is written, ``outs`` is
+        ignored and the outs returned are None.  Arguments otherwise as ``weighted_sum_sqdist``; one
+        launch.  Returns (outs, stats)."""
+        what = "centered_sum_sqdist"
+        if coef is None:
+            outs = None
+        if centers is None or len(centers) != len(segments):
+            raise ValueError(f"{what}: need one center per segment")
+        if segments and len(segments[0]):
+            for s, (seg, c) in enumerate(zip(segments, centers)):
+                self._check_center(what, c, segments[0][0].dtype, seg[0].numel() if len(seg) else 0,
+                                   f"segment {s} center")
+        # distance-only: no output to allocate -- the (checked) centers stand in, and are not written
+        dt, k, in_ptrs, numels, results = self._flat_segments(what, segments, outs if coef is not None else centers)
+        c = None if coef is None else self._sqdist_coef(what, coef, k)
+        nm = N.i64_array(numels)
+        need = int(self._lib.fa_weighted_sum_sqdist_scratch_bytes(len(segments), nm, k))
+        scratch = self._scratch("wsum_sqdist", need, stream)
+        stats = torch.empty((2, k), dtype=torch.float64, device=self.device)
+        rc = self._lib.fa_centered_sum_sqdist(self._ctx, DTYPE_CODE[dt], len(segments), nm, k, N.ptr_array(in_ptrs),
+                                              N.ptr_array([t.data_ptr() for t in centers]), c,
+                                              None if coef is None else N.ptr_array([o.data_ptr() for o in results]),
+                                              stats.data_ptr(), scratch.data_ptr(), need, self._stream(stream))
+        N.check(rc, "fa_centered_sum_sqdist")
+        return (None if coef is None else results), stats
+
+    def centered_sum_sqdist_tiled(self, buf: torch.Tensor, rows: Sequence[int], center: torch.Tensor,
+                                  coef: Optional[Sequence[float]], n: Optional[int] = None,
+                                  out: Optional[torch.Tensor] = None,
+                                  stream=None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+        """``centered_sum_sqdist`` over rows of a TILE-INTERLEAVED arena group ``buf`` [tiles, capacity,
+        E] (fa_centered_sum_sqdist_tiled): the same out, bit for bit, as over the logical rows.
+        ``center`` is flat, ``n`` elements (default: all), like ``out``, which may be ``center`` itself.
+        Returns (out, stats); ``coef`` None: distance-only, out is None.  n == 0 still makes the native
+        call: it zeroes the stats."""
+        what = "centered_sum_sqdist_tiled"
+        self._check_column_dtype(what, buf.dtype)
+        n, ptrs, stride = self._tiled_args(buf, rows, 0, n, what)
+        k = len(rows)
+        if center is None:
+            raise ValueError(f"{what}: need a center")
+        self._check_center(what, center, buf.dtype, n, "center")
+        c = None if coef is None else self._sqdist_coef(what, coef, k)
+        out = None if coef is None else self._tiled_out(what, buf, n, out)
+        nm = N.i64_array([n])
+        need = int(self._lib.fa_weighted_sum_sqdist_scratch_bytes(1, nm, k))
+        scratch = self._scratch("wsum_sqdist", need, stream)
+        stats = torch.empty((2, k), dtype=torch.float64, device=self.device)
+        rc = self._lib.fa_centered_sum_sqdist_tiled(self._ctx, DTYPE_CODE[buf.dtype], 1, nm, k, ptrs, stride,
+                                                    N.ptr_array([center.data_ptr()]), c,
+                                                    None if out is None else N.ptr_array([out.data_ptr()]),
+                                                    stats.data_ptr(), scratch.data_ptr(), need, self._stream(stream))
+        N.check(rc, "fa_centered_sum_sqdist_tiled")
+        return out, stats
+
     MAX_PAIR_K = 128  # kMaxPairK (fedml_amd/csrc/robust.hip): clients per fa_pairwise_sqdist launch
 
     def pairwise_sqdist(self, segments: Sequence[Sequence[torch.Tensor]], stream=None,

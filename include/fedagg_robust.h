@@ -11,6 +11,9 @@
  *   fa_weighted_sum_sqdist, fa_weighted_sum_sqdist_tiled  no reference code here: one smoothed Weiszfeld
  *                       pass of the geometric median (RFA), the weighted sum fused with every
  *                       client's squared distance to it
+ *   fa_centered_sum_sqdist, fa_centered_sum_sqdist_tiled  no reference code here: one pass of centered
+ *                       clipping (Karimireddy, He, Jaggi 2021) around a center the caller supplies,
+ *                       fused with every client's squared distance to the result; or the distances alone
  *   fa_pairwise_sqdist  core/security/defense/krum_defense.py:52-66 (_compute_krum_score's
  *                       compute_euclidean_distance(v_i, v_j) ** 2 for every pair)
  *   fa_pairwise_sqdist_rt  the same for bfloat16 / float16 models (differences in the model dtype)
@@ -115,6 +118,46 @@ int fa_weighted_sum_sqdist_tiled(fa_ctx *ctx, int dtype, int32_t num_segments, c
                                  void *const *d_out, void *d_stats, void *d_scratch, size_t scratch_bytes,
                                  void *hip_stream);
 size_t fa_weighted_sum_sqdist_scratch_bytes(int32_t num_segments, const int64_t *seg_numel, int32_t k);
+
+/*
+ * One pass of centered clipping (Karimireddy, He, Jaggi 2021, "Learning from History for Byzantine
+ * Robust Optimization"): the update v' = v + sum_i s_i (x_i - v) of a center v the caller supplies AND
+ * every client's squared distance to v', in one read of the inputs from HBM; with coef NULL, only the
+ * distances to v.  d_center[s]: the center of segment s, a flat contiguous tensor of seg_numel[s]
+ * elements of `dtype` (flat in the tiled entry too, like d_out[s]).  Everything else -- pointer layout,
+ * dtypes, segment rules, staging, asynchrony, error codes, d_scratch and its size
+ * (fa_weighted_sum_sqdist_scratch_bytes) -- is fa_weighted_sum_sqdist's.
+ *
+ * coef non-NULL (k host doubles, the scales s_i): bit-exact contract.  A = float32 for F32, BF16, F16,
+ * float64 for F64; rnd rounds once to the storage type; nothing is fused; coef is cast to A.  For
+ * every element e, with c = center[e]:
+ *   u_i = rnd(x_i[e] - c);  t_i = rnd(u_i * (A)coef_i)
+ *   acc = t_0;  acc = rnd(acc + t_i) for i = 1 .. k-1 in client order
+ *   out[e] = rnd(c + acc)
+ *   d_stats[i] = sum_e (x_i[e] - out[e])^2 against the STORED out;  d_stats[k + i] = sum_e x_i[e]^2
+ * with fa_weighted_sum_sqdist's arithmetic, fixed order and 1e-6 bound for the sums (an exact 0 gives
+ * 0; tests/test_gpu_centered_clipping.py).  d_out[s] may be the very pointer d_center[s] (an in-place
+ * update: each element is read and then written by the one lane that owns it); no other overlap of
+ * d_out with d_center or d_in is allowed.
+ *
+ * coef NULL (distance-only): d_out is ignored and may be NULL; nothing but d_stats is written:
+ *   d_stats[i] = sum_e (x_i[e] - center[e])^2;  d_stats[k + i] = sum_e x_i[e]^2.
+ *
+ * All segments empty: d_stats is zeroed.  Checked before any HIP call, in this order: ctx; (tiled)
+ * tile_stride > 0; k, num_segments, seg_numel, d_in (and d_out when coef is given); d_center; d_stats;
+ * dtype (I64: FA_ERR_DTYPE); (tiled) tile_stride a multiple of FA_TILE_BYTES; per non-empty segment
+ * its center, output and input pointers; the scratch.
+ */
+int fa_centered_sum_sqdist(fa_ctx *ctx, int dtype, int32_t num_segments, const int64_t *seg_numel, int32_t k,
+                           const void *const *d_in, const void *const *d_center, const double *coef,
+                           void *const *d_out, void *d_stats, void *d_scratch, size_t scratch_bytes,
+                           void *hip_stream);
+/* The same over tile-interleaved client rows (addressing and tile rules of fa_coord_median_tiled):
+ * out bit for bit fa_centered_sum_sqdist's over the logical rows, the sums within the same bound. */
+int fa_centered_sum_sqdist_tiled(fa_ctx *ctx, int dtype, int32_t num_segments, const int64_t *seg_numel, int32_t k,
+                                 const void *const *d_in, int64_t tile_stride, const void *const *d_center,
+                                 const double *coef, void *const *d_out, void *d_stats, void *d_scratch,
+                                 size_t scratch_bytes, void *hip_stream);
 
 /*
  * Pairwise squared Euclidean distances of k float32 client vectors (2 <= k <= 128), each given
