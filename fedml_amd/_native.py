@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = (
     "fa_mt_randint_sum_scratch_bytes",
     # include/fedagg_robust.h
     "fa_coord_median", "fa_coord_median_tiled", "fa_coord_trimmed_mean", "fa_coord_trimmed_mean_tiled",
+    "fa_coord_mean_around_median", "fa_coord_mean_around_median_tiled",
     "fa_weighted_sum_sqdist", "fa_weighted_sum_sqdist_tiled", "fa_weighted_sum_sqdist_scratch_bytes", "fa_pairwise_sqdist", "fa_pairwise_sqdist_rt", "fa_pairwise_sqdist_scratch_bytes",
     "fa_centered_sum_sqdist", "fa_centered_sum_sqdist_tiled",
     "fa_pairwise_sqdist_gram", "fa_pairwise_sqdist_gram_scratch_bytes", "fa_pairwise_sqdist_gram_limit",
@@ -171,6 +172,10 @@ def _declare(L):
     L.fa_coord_trimmed_mean_tiled.restype = ctypes.c_int
     L.fa_coord_trimmed_mean_tiled.argtypes = [_vp, ctypes.c_int, ctypes.c_int32, _P_i64, ctypes.c_int32, ctypes.c_int32,
                                               _P_vp, ctypes.c_int64, _P_vp, _vp]
+    L.fa_coord_mean_around_median.restype = ctypes.c_int
+    L.fa_coord_mean_around_median.argtypes = L.fa_coord_trimmed_mean.argtypes
+    L.fa_coord_mean_around_median_tiled.restype = ctypes.c_int
+    L.fa_coord_mean_around_median_tiled.argtypes = L.fa_coord_trimmed_mean_tiled.argtypes
     L.fa_weighted_sum_sqdist.restype = ctypes.c_int
     L.fa_weighted_sum_sqdist.argtypes = [_vp, ctypes.c_int, ctypes.c_int32, _P_i64, ctypes.c_int32, _P_vp, _P_d, _P_vp,
                                          _vp, _vp, ctypes.c_size_t, _vp]

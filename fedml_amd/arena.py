@@ -494,7 +494,7 @@ class ClientArena:
         return self.layout.carve(outs)
 
     def _column_op(self, what: str, clients, no_clients: Exception, out, *trim) -> "OrderedDict[str, torch.Tensor]":
-        """median / trimmed_mean: the engine's coord_<what>[_tiled] over every dtype group."""
+        """median / trimmed_mean / mean_around_median: the engine's coord_<what>[_tiled] over every dtype group."""
         clients = list(range(self.capacity)) if clients is None else list(clients)
         if not clients:
             raise no_clients
@@ -530,6 +530,15 @@ class ClientArena:
         per dtype group: tiled arenas through fa_coord_trimmed_mean_tiled, client-major arenas over the
         row views.  Float groups only.  Returns per-key views."""
         return self._column_op("trimmed_mean", clients, ValueError("trimmed_mean: no client rows"), out, trim)
+
+    def mean_around_median(self, keep: int, clients: Optional[Sequence[int]] = None,
+                           out: Optional[Dict[torch.dtype, torch.Tensor]] = None) -> "OrderedDict[str, torch.Tensor]":
+        """Coordinate-wise mean of the ``keep`` values nearest to the median (Bulyan's second stage;
+        include/fedagg_robust.h) over the given client rows (default: all), read in place, one launch per
+        dtype group: tiled arenas through fa_coord_mean_around_median_tiled, client-major arenas over the
+        row views.  Float groups only.  Returns per-key views."""
+        return self._column_op("mean_around_median", clients, ValueError("mean_around_median: no client rows"), out,
+                               keep)
 
     def geometric_median(self, counts: Sequence[float], iters: int = 3, nu: float = 1e-6,
                          clients: Optional[Sequence[int]] = None,

@@ -6,7 +6,10 @@ sample-weighted geometric median by the smoothed Weiszfeld iteration of Pillutla
 geomed_iters, geomed_nu; the reference's own RFA name stays unserved) and centered_clipping (centered
 clipping of Karimireddy et al. around the global model or the mean, one iteration of which is
 norm-difference clipping followed by FedAvg; config cclip_tau, cclip_iters, cclip_center; the
-reference's cclip and norm_diff_clipping names stay unserved).  Same dispatch
+reference's cclip and norm_diff_clipping names stay unserved) and bulyan (El Mhamdi et al. 2018: Krum
+repeated over one distance matrix, then per coordinate the mean of the values nearest the median over
+the chosen clients; config byzantine_client_num; the contract is the paper's as written in
+fedagg_robust.h and is not pinned to a reference fixture).  Same dispatch
 (which defenses act before / on / after aggregation) and the same entry points; the per-element work
 runs in the HIP kernels (fedml_amd/csrc/median.hip, trimmed.hip, wsum_dist.hip, robust.hip).  Other
 defense types of the reference are outside the aggregation path and raise NotImplementedError when
@@ -18,8 +21,10 @@ import logging
 from collections import OrderedDict
 from typing import Any, Callable, List, Tuple
 
-from .constants import (DEFENSE_CENTERED_CLIPPING, DEFENSE_COORD_TRIMMED_MEAN, DEFENSE_GEOMETRIC_MEDIAN, DEFENSE_KRUM,
-                        DEFENSE_MULTIKRUM, DEFENSE_TRIMMED_MEAN, DEFENSE_WISE_MEDIAN)
+from .constants import (DEFENSE_BULYAN, DEFENSE_CENTERED_CLIPPING, DEFENSE_COORD_TRIMMED_MEAN,
+                        DEFENSE_GEOMETRIC_MEDIAN, DEFENSE_KRUM, DEFENSE_MULTIKRUM, DEFENSE_TRIMMED_MEAN,
+                        DEFENSE_WISE_MEDIAN)
+from .defense.bulyan_defense import BulyanDefense
 from .defense.centered_clipping_defense import CenteredClippingDefense
 from .defense.coordinate_trimmed_mean_defense import CoordinateTrimmedMeanDefense
 from .defense.coordinate_wise_median_defense import CoordinateWiseMedianDefense
@@ -60,11 +65,13 @@ class FedMLDefender:
                 self.defender = GeometricMedianDefense(args)
             elif self.defense_type == DEFENSE_CENTERED_CLIPPING:
                 self.defender = CenteredClippingDefense(args)
+            elif self.defense_type == DEFENSE_BULYAN:
+                self.defender = BulyanDefense(args)
             else:
                 raise NotImplementedError(
                     f"defense_type {self.defense_type!r} is not served by the MI355X engine "
                     f"(supported: krum, multikrum, trimmed_mean, wise_median, coordinate_trimmed_mean, "
-                    f"geometric_median, centered_clipping)")
+                    f"geometric_median, centered_clipping, bulyan)")
         else:
             self.is_enabled = False
             self.defense_type = None
@@ -77,7 +84,8 @@ class FedMLDefender:
         return self.is_defense_enabled() and self.defense_type in [DEFENSE_WISE_MEDIAN,
                                                                                DEFENSE_COORD_TRIMMED_MEAN,
                                                                                DEFENSE_GEOMETRIC_MEDIAN,
-                                                                               DEFENSE_CENTERED_CLIPPING]
+                                                                               DEFENSE_CENTERED_CLIPPING,
+                                                                               DEFENSE_BULYAN]
 
     def is_defense_before_aggregation(self):
         return self.is_defense_enabled() and self.defense_type in [DEFENSE_KRUM, DEFENSE_MULTIKRUM,

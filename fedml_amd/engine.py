@@ -864,6 +864,12 @@ class AggEngine:
             raise ValueError(f"{what}: trim must be an integer with 0 <= trim and 2 * trim < K (trim {trim}, K {k})")
         return int(trim)
 
+    @staticmethod
+    def _check_keep(keep, k: int, what: str) -> int:
+        if int(keep) != keep or not 1 <= keep <= k:
+            raise ValueError(f"{what}: keep must be an integer with 1 <= keep <= K (keep {keep}, K {k})")
+        return int(keep)
+
     def _check_column_dtype(self, what: str, dt) -> None:
         if dt not in self._COLUMN_DTYPES:
             raise TypeError(f"{what}: unsupported dtype {dt}")
@@ -906,22 +912,24 @@ class AggEngine:
         _require_device(out, self.device, "output")
         return out
 
-    def _column_op(self, what: str, segments, outs, stream, *trim) -> List[torch.Tensor]:
+    def _column_op(self, what: str, segments, outs, stream, *trim, check=None) -> List[torch.Tensor]:
         """The flat per-column operators (``what`` = coord_median, or coord_trimmed_mean followed by
-        its ``trim``): one launch of fa_<what>."""
+        its ``trim``, or coord_mean_around_median followed by its ``keep`` with ``check`` =
+        _check_keep): one launch of fa_<what>."""
         dt, k, in_ptrs, numels, results = self._flat_segments(what, segments, outs)
-        trim = [self._check_trim(b, k, what) for b in trim]
+        trim = [(check or self._check_trim)(b, k, what) for b in trim]
         rc = getattr(self._lib, "fa_" + what)(self._ctx, DTYPE_CODE[dt], len(segments), N.i64_array(numels), k, *trim,
                                               N.ptr_array(in_ptrs), N.ptr_array([o.data_ptr() for o in results]),
                                               self._stream(stream))
         N.check(rc, "fa_" + what)
         return results
 
-    def _column_op_tiled(self, what: str, buf: torch.Tensor, rows, n, out, stream, *trim) -> torch.Tensor:
+    def _column_op_tiled(self, what: str, buf: torch.Tensor, rows, n, out, stream, *trim, check=None) -> torch.Tensor:
         """The tiled per-column operators (``what`` = coord_median_tiled, or coord_trimmed_mean_tiled
-        followed by its ``trim``) over rows of a tile-interleaved arena group: one launch of fa_<what>."""
+        followed by its ``trim``, or coord_mean_around_median_tiled followed by its ``keep`` with
+        ``check`` = _check_keep) over rows of a tile-interleaved arena group: one launch of fa_<what>."""
         self._check_column_dtype(what, buf.dtype)
-        trim = [self._check_trim(b, len(rows), what) for b in trim]
+        trim = [(check or self._check_trim)(b, len(rows), what) for b in trim]
         n, ptrs, stride = self._tiled_args(buf, rows, 0, n, what)
         out = self._tiled_out(what, buf, n, out)
         if n == 0:
@@ -958,6 +966,25 @@ class AggEngine:
         capacity, E] (fa_coord_trimmed_mean_tiled): bit for bit ``coord_trimmed_mean`` over the
         logical rows.  Arguments and results as ``coord_median_tiled``."""
         return self._column_op_tiled("coord_trimmed_mean_tiled", buf, rows, n, out, stream, trim)
+
+    def coord_mean_around_median(self, segments: Sequence[Sequence[torch.Tensor]], keep: int,
+                                 outs: Optional[Sequence[torch.Tensor]] = None, stream=None) -> List[torch.Tensor]:
+        """Coordinate-wise mean around the median over clients (fa_coord_mean_around_median; the second
+        stage of Bulyan, El Mhamdi et al. 2018): per coordinate the K values sorted (NaN largest), the
+        window of ``keep`` consecutive ranks nearest to the lower median s[(K-1)/2] (ties to the lower
+        side), summed in rank order in float64 from its first value, divided by ``keep`` and rounded to
+        the dtype (include/fedagg_robust.h).  1 <= keep <= K.  Arguments and results as ``coord_median``."""
+        return self._column_op("coord_mean_around_median", segments, outs, stream, keep, check=self._check_keep)
+
+    def coord_mean_around_median_tiled(self, buf: torch.Tensor, rows: Sequence[int], keep: int,
+                                       n: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                                       stream=None) -> torch.Tensor:
+        """Coordinate-wise mean around the median over rows of a TILE-INTERLEAVED arena group ``buf``
+        [tiles, capacity, E] (fa_coord_mean_around_median_tiled): bit for bit
+        ``coord_mean_around_median`` over the logical rows.  Arguments and results as
+        ``coord_median_tiled``."""
+        return self._column_op_tiled("coord_mean_around_median_tiled", buf, rows, n, out, stream, keep,
+                                     check=self._check_keep)
 
     def _sqdist_coef(self, what: str, coef, k: int):
         if coef is None or len(coef) != k:

@@ -8,6 +8,8 @@
  *   fa_coord_median_tiled  the same over tile-interleaved arena rows
  *   fa_coord_trimmed_mean, fa_coord_trimmed_mean_tiled  no reference code: the per-coordinate trimmed
  *                       mean of Yin et al. 2018 (the reference's "trimmed mean" trims whole clients)
+ *   fa_coord_mean_around_median, fa_coord_mean_around_median_tiled  no reference code here: the second
+ *                       stage of Bulyan (El Mhamdi et al. 2018), the mean of the values nearest the median
  *   fa_weighted_sum_sqdist, fa_weighted_sum_sqdist_tiled  no reference code here: one smoothed Weiszfeld
  *                       pass of the geometric median (RFA), the weighted sum fused with every
  *                       client's squared distance to it
@@ -83,6 +85,41 @@ int fa_coord_trimmed_mean(fa_ctx *ctx, int dtype, int32_t num_segments, const in
 int fa_coord_trimmed_mean_tiled(fa_ctx *ctx, int dtype, int32_t num_segments, const int64_t *seg_numel,
                                 int32_t k, int32_t trim, const void *const *d_in, int64_t tile_stride,
                                 void *const *d_out, void *hip_stream);
+
+/*
+ * Coordinate-wise mean around the median: per coordinate the mean of the `keep` values nearest to the
+ * column's median, 1 <= keep <= k (else FA_ERR_INVALID) -- the second stage of Bulyan (El Mhamdi,
+ * Guerraoui, Rouault 2018, "The Hidden Vulnerability of Distributed Learning in Byzantium") over the
+ * clients its first stage selected (fedml_amd/bulyan.py), keep = theta - 2f.  Pointer layout
+ * d_in[s * k + i], dtypes (F32, BF16, F16, F64), segment rules, asynchrony on the caller's stream,
+ * validation before any HIP call (the context first), error codes: fa_coord_trimmed_mean's.  Contract
+ * (bit-exact; tests/test_gpu_mean_around_median.py), for every element e:
+ *   1. s = the k values of the column ordered ascending as in fa_coord_trimmed_mean: -0.0 below +0.0,
+ *      NaN (any sign or payload) above +inf, the order of equal values immaterial;
+ *   2. h = (k - 1) / 2 (integer division), m = s[h], the lower median; m NaN: the result is NaN;
+ *   3. dist(v) = 0 if v == m (an IEEE comparison: equal infinities and -0.0 / +0.0 are at distance 0),
+ *      +inf if v is NaN, otherwise |(double)v - (double)m|, one float64 subtraction (F64: it may
+ *      overflow to +inf);
+ *   4. lomin = max(0, h - keep + 1), lomax = min(h, k - keep),
+ *      lo = lomin + #{ r in [lomin, lomax) : dist(s[r]) > dist(s[r + keep]) }:
+ *      the window of `keep` consecutive ranks that greedy growth from rank h reaches when it takes the
+ *      nearer outside neighbour and the lower one on a tie.  The restriction of r to [lomin, lomax) is
+ *      part of the contract: every finite distance to an infinite median saturates to +inf, and
+ *      [1, 2, 3, 4, inf, inf, inf, inf, inf] with keep = 2 must give {inf, inf}, not {3, 4};
+ *   5. acc = (double)s[lo]; acc += (double)s[r] for r = lo+1 .. lo+keep-1, in that order;
+ *      q = acc / (double)keep; out[e] = q stored as fa_coord_trimmed_mean stores it (F64 as is, F32 one
+ *      rounding, BF16 / F16 float64 -> float32 -> 16 bits, round-to-nearest-even).
+ * A NaN inside the window gives NaN (bits unspecified), as does a window holding both +inf and -inf.
+ * keep = k is fa_coord_trimmed_mean with trim 0, bit for bit, and keep = 1 on odd k is
+ * fa_coord_trimmed_mean with trim (k - 1) / 2.  Sample counts play no part.
+ */
+int fa_coord_mean_around_median(fa_ctx *ctx, int dtype, int32_t num_segments, const int64_t *seg_numel,
+                                int32_t k, int32_t keep, const void *const *d_in, void *const *d_out,
+                                void *hip_stream);
+/* The same over tile-interleaved client rows (addressing and tile rules of fa_coord_median_tiled). */
+int fa_coord_mean_around_median_tiled(fa_ctx *ctx, int dtype, int32_t num_segments, const int64_t *seg_numel,
+                                      int32_t k, int32_t keep, const void *const *d_in, int64_t tile_stride,
+                                      void *const *d_out, void *hip_stream);
 
 /*
  * One pass of the smoothed Weiszfeld iteration for the geometric median (Pillutla, Kakade, Harchaoui,
