@@ -30,6 +30,7 @@ H2D per dtype group is issued on a copy stream, and the aggregation stream waits
 """
 from __future__ import annotations
 
+import math
 import os
 import weakref
 from collections import OrderedDict
@@ -119,6 +120,19 @@ def sum_stats(stats: Sequence[torch.Tensor]) -> Tuple[List[float], List[float]]:
         d2 = [a + b for a, b in zip(d2, g[0])]
         ss = [a + b for a, b in zip(ss, g[1])]
     return d2, ss
+
+
+def sign_vote_coef(counts: Sequence[float], server_lr: float) -> List[float]:
+    """The robust learning rate's coefficients: server_lr * counts_i / sum(counts), float64, evaluated
+    left to right (``ClientArena.sign_vote_sum`` and ``RobustLearningRateDefense`` share them)."""
+    counts = [float(c) for c in counts]
+    if not all(c > 0 and math.isfinite(c) for c in counts):
+        raise ValueError("robust_lr: every client weight must be positive and finite")
+    if isinstance(server_lr, bool) or not isinstance(server_lr, (int, float)) or \
+            not (server_lr > 0 and math.isfinite(server_lr)):
+        raise ValueError(f"robust_lr: server_lr must be a positive finite number (got {server_lr!r})")
+    total = sum(counts)
+    return [float(server_lr) * c / total for c in counts]
 
 
 def tile_elems(dt: torch.dtype) -> int:
@@ -648,6 +662,68 @@ class ClientArena:
         res = cclip_driver(counts, iters, tau, first, lambda scales, idx: run(idx, scales, True))
         if info is not None:
             info.update(res)
+        return self.layout.carve(outs)
+
+    def sign_vote_sum(self, counts: Sequence[float], threshold: int, server_lr: float = 1.0,
+                      center: Optional[Dict[torch.dtype, torch.Tensor]] = None,
+                      clients: Optional[Sequence[int]] = None,
+                      out: Optional[Dict[torch.dtype, torch.Tensor]] = None,
+                      info: Optional[dict] = None) -> "OrderedDict[str, torch.Tensor]":
+        """The robust learning rate (Ozdayi, Kantarcioglu, Gel 2021; include/fedagg_robust.h,
+        fa_sign_vote_sum) over the given client rows (default: all) weighted by ``counts`` (aligned with
+        ``clients``): center + eta * sum_i w_i (x_i - center) with w_i = counts_i / sum(counts) and, per
+        element, eta = -server_lr where the net vote of the K signs of x_i - center is below
+        ``threshold`` and +server_lr elsewhere.  ``center``: dtype -> flat device tensor of the group's
+        elements in the layout's order (only read, unless it is ``out`` itself); None: the votes and the sum are over
+        the rows' own values.  ONE launch per dtype group: tiled arenas through the tiled entry,
+        client-major arenas over the row views.  Float groups only.  ``info`` (optional dict) receives
+        ``flipped`` (the number of negated elements) and ``elements``, summed over the groups' keys
+        (their alignment padding left out, at the price of one small launch over the padding per
+        group).  Returns per-key views."""
+        rows = list(range(self.capacity)) if clients is None else list(clients)
+        if not rows:
+            raise ValueError("robust_lr: no client rows")
+        if len(counts) != len(rows):
+            raise ValueError("robust_lr: need one count per client row")
+        if any(dt not in (torch.float32, torch.bfloat16, torch.float16, torch.float64) for dt in self.bufs):
+            raise TypeError("robust_lr: the arena holds a non-float dtype group")
+        if center is not None:
+            for dt in self.bufs:
+                c = center.get(dt)
+                n = self.layout.group_numel[dt]
+                if c is None or c.dtype != dt or c.numel() != n or not c.is_contiguous():
+                    raise ValueError(f"robust_lr: center[{dt}] must be a contiguous {dt} tensor of {n} elements")
+        coef = sign_vote_coef(counts, server_lr)
+        self._wait_ingest()
+        outs: Dict[torch.dtype, torch.Tensor] = {}
+        flips, pad_flips = [], []
+        for dt, buf in self.bufs.items():
+            n = self.layout.group_numel[dt]
+            o = out[dt] if out is not None else None
+            c = center[dt].reshape(-1) if center is not None else None
+            # the keys' alignment padding takes part in the group's launch and its count; when the
+            # count is asked for, one small launch over the padding alone (each range lies inside one
+            # tile, so it is contiguous in both layouts), before the center can be updated in place,
+            # says how much of it to take off
+            pads = [(off + kn, off + _pad(max(kn, 1))) for kdt, off, _, kn in self.layout.where.values()
+                    if kdt == dt and _pad(max(kn, 1)) > kn] if info is not None else []
+            if pads:
+                E = tile_elems(dt)
+                segs = [[buf[a // E, r, a % E:a % E + b - a] if self.tiled else buf[r][a:b] for r in rows]
+                        for a, b in pads]
+                pad_flips.append(self.engine.sign_vote_sum(segs, None if c is None else [c[a:b] for a, b in pads],
+                                                           coef, threshold)[1])
+            if self.tiled:
+                outs[dt], f = self.engine.sign_vote_sum_tiled(buf, rows, c, coef, threshold, n=n, out=o)
+            else:
+                o = o if o is not None else torch.empty(n, dtype=dt, device=buf.device)
+                f = self.engine.sign_vote_sum([[buf[i][:n] for i in rows]], None if c is None else [c], coef,
+                                              threshold, outs=[o])[1]
+                outs[dt] = o
+            flips.append(f)
+        if info is not None:
+            info.update(flipped=sum(int(f.item()) for f in flips) - sum(int(f.item()) for f in pad_flips),
+                        elements=sum(kn for _, _, _, kn in self.layout.where.values()))
         return self.layout.carve(outs)
 
     def _pair_groups(self) -> Optional[torch.dtype]:

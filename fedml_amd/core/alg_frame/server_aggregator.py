@@ -71,7 +71,8 @@ class ServerAggregator(ABC):
 
     def aggregate(self, raw_client_model_or_grad_list: List[Tuple[float, OrderedDict]]):
         """Reference :67-76 -> the on-aggregation defense (wise_median, coordinate_trimmed_mean, geometric_median,
-        bulyan, centered_clipping, whose center is the global model passed here) or FedMLAggOperator.agg."""
+        bulyan, and centered_clipping and robust_lr, whose center is the global model passed here) or
+        FedMLAggOperator.agg."""
         d = FedMLDefender.get_instance()
         if d.is_defense_enabled():
             return d.defend_on_aggregation(raw_client_grad_list=raw_client_model_or_grad_list,

@@ -7,3 +7,4 @@ DEFENSE_COORD_TRIMMED_MEAN = "coordinate_trimmed_mean"  # no reference name: the
 DEFENSE_GEOMETRIC_MEDIAN = "geometric_median"  # no reference name here (its RFA stays unserved): smoothed Weiszfeld, contract in fedagg_robust.h
 DEFENSE_CENTERED_CLIPPING = "centered_clipping"  # no reference name here (its cclip and norm_diff_clipping stay unserved): contract in fedagg_robust.h
 DEFENSE_BULYAN = "bulyan"  # no reference fixture: the contract is the paper's (El Mhamdi et al. 2018) as written in fedagg_robust.h
+DEFENSE_ROBUST_LR = "robust_lr"  # no reference name here (its robust_learning_rate stays unserved): the sign-vote learning rate of Ozdayi et al. 2021, contract in fedagg_robust.h

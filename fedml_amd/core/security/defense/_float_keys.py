@@ -1,5 +1,5 @@
 """The scaffold shared by the defenses that run one engine operator over every floating-point key of
-the clients' dicts (coordinate_trimmed_mean_defense.py, geometric_median_defense.py, centered_clipping_defense.py, bulyan_defense.py): which keys take
+the clients' dicts (coordinate_trimmed_mean_defense.py, geometric_median_defense.py, centered_clipping_defense.py, bulyan_defense.py, robust_lr_defense.py): which keys take
 part, the resident-arena form, the per-dtype segments of the engine form, and the way back to a dict.
 """
 from __future__ import annotations

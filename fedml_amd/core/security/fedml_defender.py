@@ -9,9 +9,13 @@ norm-difference clipping followed by FedAvg; config cclip_tau, cclip_iters, ccli
 reference's cclip and norm_diff_clipping names stay unserved) and bulyan (El Mhamdi et al. 2018: Krum
 repeated over one distance matrix, then per coordinate the mean of the values nearest the median over
 the chosen clients; config byzantine_client_num; the contract is the paper's as written in
-fedagg_robust.h and is not pinned to a reference fixture).  Same dispatch
+fedagg_robust.h and is not pinned to a reference fixture) and robust_lr (the robust learning rate of
+Ozdayi et al. 2021 against backdoors: per coordinate the clients' updates vote with their signs and
+the server's learning rate is negated where fewer than robust_lr_threshold net votes agree; config
+robust_lr_threshold (required), robust_lr_server_lr, robust_lr_center; the reference's own
+robust_learning_rate name stays unserved).  Same dispatch
 (which defenses act before / on / after aggregation) and the same entry points; the per-element work
-runs in the HIP kernels (fedml_amd/csrc/median.hip, trimmed.hip, wsum_dist.hip, robust.hip).  Other
+runs in the HIP kernels (fedml_amd/csrc/median.hip, trimmed.hip, wsum_dist.hip, signvote.hip, robust.hip).  Other
 defense types of the reference are outside the aggregation path and raise NotImplementedError when
 configured.
 """
@@ -22,8 +26,8 @@ from collections import OrderedDict
 from typing import Any, Callable, List, Tuple
 
 from .constants import (DEFENSE_BULYAN, DEFENSE_CENTERED_CLIPPING, DEFENSE_COORD_TRIMMED_MEAN,
-                        DEFENSE_GEOMETRIC_MEDIAN, DEFENSE_KRUM, DEFENSE_MULTIKRUM, DEFENSE_TRIMMED_MEAN,
-                        DEFENSE_WISE_MEDIAN)
+                        DEFENSE_GEOMETRIC_MEDIAN, DEFENSE_KRUM, DEFENSE_MULTIKRUM, DEFENSE_ROBUST_LR,
+                        DEFENSE_TRIMMED_MEAN, DEFENSE_WISE_MEDIAN)
 from .defense.bulyan_defense import BulyanDefense
 from .defense.centered_clipping_defense import CenteredClippingDefense
 from .defense.coordinate_trimmed_mean_defense import CoordinateTrimmedMeanDefense
@@ -31,6 +35,7 @@ from .defense.coordinate_wise_median_defense import CoordinateWiseMedianDefense
 from .defense.coordinate_wise_trimmed_mean_defense import CoordinateWiseTrimmedMeanDefense
 from .defense.geometric_median_defense import GeometricMedianDefense
 from .defense.krum_defense import KrumDefense
+from .defense.robust_lr_defense import RobustLearningRateDefense
 
 
 class FedMLDefender:
@@ -67,11 +72,13 @@ class FedMLDefender:
                 self.defender = CenteredClippingDefense(args)
             elif self.defense_type == DEFENSE_BULYAN:
                 self.defender = BulyanDefense(args)
+            elif self.defense_type == DEFENSE_ROBUST_LR:
+                self.defender = RobustLearningRateDefense(args)
             else:
                 raise NotImplementedError(
                     f"defense_type {self.defense_type!r} is not served by the MI355X engine "
                     f"(supported: krum, multikrum, trimmed_mean, wise_median, coordinate_trimmed_mean, "
-                    f"geometric_median, centered_clipping, bulyan)")
+                    f"geometric_median, centered_clipping, bulyan, robust_lr)")
         else:
             self.is_enabled = False
             self.defense_type = None
@@ -85,7 +92,8 @@ class FedMLDefender:
                                                                                DEFENSE_COORD_TRIMMED_MEAN,
                                                                                DEFENSE_GEOMETRIC_MEDIAN,
                                                                                DEFENSE_CENTERED_CLIPPING,
-                                                                               DEFENSE_BULYAN]
+                                                                               DEFENSE_BULYAN,
+                                                                               DEFENSE_ROBUST_LR]
 
     def is_defense_before_aggregation(self):
         return self.is_defense_enabled() and self.defense_type in [DEFENSE_KRUM, DEFENSE_MULTIKRUM,

@@ -1,8 +1,9 @@
 // median_host.h -- the host path shared by the C entries that launch over an MSeg table (median.hip,
-// trimmed.hip, wsum_dist.hip): argument checks, the grid for a given element count per workgroup,
-// the MSeg + pointer table (and an entry's own payload) in a staging slot, and the launch.  An entry
-// checks in this order: col_check_args (NULL context, then the other arguments), its own arguments
-// (the trim; d_center, coef and d_stats), col_count (dtype, tile_stride, then the segments), its scratch.
+// trimmed.hip, wsum_dist.hip, signvote.hip): argument checks, the grid for a given element count per
+// workgroup, the MSeg + pointer table (and an entry's own payload) in a staging slot, and the launch.
+// An entry checks in this order: col_check_args (NULL context, then the other arguments), its own
+// arguments (the trim; d_center, coef and d_stats; coef and the threshold), col_count (dtype,
+// tile_stride, then the segments), its scratch.
 // Not part of the ABI.
 #pragma once
 
@@ -23,7 +24,7 @@ struct ColArgs {
   int64_t tstride;          // 0: flat segments; > 0: tile-interleaved inputs
   void* const* d_out;
   void* hip_stream;
-  // wsum_dist.hip's centered entries: [num_segments] flat tensors, checked with the segments and
+  // wsum_dist.hip's and signvote.hip's centered entries: [num_segments] flat tensors, checked with the segments and
   // part of a segment's `aligned`; the entry stages the pointers in its own payload, so the
   // tables staged here do not depend on them.  NULL: no center.
   const void* const* d_center = nullptr;
@@ -66,10 +67,12 @@ static inline int col_count(const ColArgs& a, int64_t cols, int* nseg, int64_t* 
 // After col_count found nseg > 0 segments and `tiles` workgroups: stages the segment and pointer
 // tables of the non-empty segments, followed by `extra` bytes (8-byte aligned) that fill(host
 // address) writes (the copy is skipped when the slot already holds all of it), and calls
-// launch(grid, stream, segs, nseg, ptrs, the payload's device address).
+// launch(grid, stream, segs, nseg, ptrs, the payload's device address).  `scratch` more bytes of the
+// slot's device buffer follow the payload (at its address + extra): never copied, theirs to write for
+// the kernels launched here (signvote.hip: the per-workgroup counts).
 template <class Fill, class Launch>
 int col_stage_launch(const ColArgs& a, int64_t cols, int nseg, int64_t tiles, size_t extra, Fill fill,
-                     Launch launch) {
+                     Launch launch, size_t scratch = 0) {
   const int k = a.k;
   const size_t seg_bytes = align16(sizeof(MSeg) * nseg);
   const size_t ptr_bytes = sizeof(void*) * (size_t)nseg * k;
@@ -77,7 +80,7 @@ int col_stage_launch(const ColArgs& a, int64_t cols, int nseg, int64_t tiles, si
   if (!g.ok) return fail(FA_ERR_HIP, "hipSetDevice(%d) failed", a.ctx->device);
   hipStream_t st = (hipStream_t)a.hip_stream;
   fa_ctx::Slot* slot = nullptr;
-  int rc = acquire_slot(a.ctx, seg_bytes + ptr_bytes + extra, &slot);
+  int rc = acquire_slot(a.ctx, seg_bytes + ptr_bytes + extra + scratch, &slot);
   if (rc) return rc;
   char* h = (char*)slot->host;
   MSeg* hs = (MSeg*)h;

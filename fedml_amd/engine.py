@@ -1104,6 +1104,68 @@ class AggEngine:
         N.check(rc, "fa_centered_sum_sqdist_tiled")
         return out, stats
 
+    def _check_threshold(self, what: str, threshold, k: int) -> int:
+        if isinstance(threshold, bool) or not isinstance(threshold, int) or not 0 <= threshold <= k:
+            raise ValueError(f"{what}: threshold must be an integer with 0 <= threshold <= K "
+                             f"(threshold {threshold!r}, K {k})")
+        return threshold
+
+    def sign_vote_sum(self, segments: Sequence[Sequence[torch.Tensor]], centers: Optional[Sequence[torch.Tensor]],
+                      coef: Sequence[float], threshold: int, outs: Optional[Sequence[torch.Tensor]] = None,
+                      stream=None) -> Tuple[List[torch.Tensor], torch.Tensor]:
+        """The robust learning rate's pass (fa_sign_vote_sum): the ordered sum of coef_i u_i with
+        u_i = x_i - center rounded in the dtype (``centers`` None: u_i = x_i), negated at every element
+        where the net vote |sum_i sign(u_i)| is below ``threshold``, and added to the center
+        (include/fedagg_robust.h).  centers[s]: segment s's center, the segment's dtype and element
+        count; outs[s] may be centers[s] itself (in place).  0 <= threshold <= K.  Arguments otherwise
+        as ``weighted_sum_sqdist``; one launch.  Returns (outs, flipped): flipped is a one-element
+        int64 device tensor, the number of negated elements over all segments."""
+        what = "sign_vote_sum"
+        if centers is not None:
+            if len(centers) != len(segments):
+                raise ValueError(f"{what}: need one center per segment")
+            if segments and len(segments[0]):
+                for s, (seg, c) in enumerate(zip(segments, centers)):
+                    self._check_center(what, c, segments[0][0].dtype, seg[0].numel() if len(seg) else 0,
+                                       f"segment {s} center")
+        dt, k, in_ptrs, numels, results = self._flat_segments(what, segments, outs)
+        c = self._sqdist_coef(what, coef, k)
+        threshold = self._check_threshold(what, threshold, k)
+        flipped = torch.empty(1, dtype=torch.int64, device=self.device)
+        rc = self._lib.fa_sign_vote_sum(self._ctx, DTYPE_CODE[dt], len(segments), N.i64_array(numels), k,
+                                        N.ptr_array(in_ptrs),
+                                        None if centers is None else N.ptr_array([t.data_ptr() for t in centers]), c,
+                                        threshold, N.ptr_array([o.data_ptr() for o in results]), flipped.data_ptr(),
+                                        self._stream(stream))
+        N.check(rc, "fa_sign_vote_sum")
+        return results, flipped
+
+    def sign_vote_sum_tiled(self, buf: torch.Tensor, rows: Sequence[int], center: Optional[torch.Tensor],
+                            coef: Sequence[float], threshold: int, n: Optional[int] = None,
+                            out: Optional[torch.Tensor] = None,
+                            stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``sign_vote_sum`` over rows of a TILE-INTERLEAVED arena group ``buf`` [tiles, capacity, E]
+        (fa_sign_vote_sum_tiled): the same out and count, bit for bit, as over the logical rows.
+        ``center`` (or None) is flat, ``n`` elements (default: all), like ``out``, which may be
+        ``center`` itself.  Returns (out, flipped).  n == 0 still makes the native call: it zeroes the
+        count."""
+        what = "sign_vote_sum_tiled"
+        self._check_column_dtype(what, buf.dtype)
+        n, ptrs, stride = self._tiled_args(buf, rows, 0, n, what)
+        k = len(rows)
+        if center is not None:
+            self._check_center(what, center, buf.dtype, n, "center")
+        c = self._sqdist_coef(what, coef, k)
+        threshold = self._check_threshold(what, threshold, k)
+        out = self._tiled_out(what, buf, n, out)
+        flipped = torch.empty(1, dtype=torch.int64, device=self.device)
+        rc = self._lib.fa_sign_vote_sum_tiled(self._ctx, DTYPE_CODE[buf.dtype], 1, N.i64_array([n]), k, ptrs, stride,
+                                              None if center is None else N.ptr_array([center.data_ptr()]), c,
+                                              threshold, N.ptr_array([out.data_ptr()]), flipped.data_ptr(),
+                                              self._stream(stream))
+        N.check(rc, "fa_sign_vote_sum_tiled")
+        return out, flipped
+
     MAX_PAIR_K = 128  # kMaxPairK (fedml_amd/csrc/robust.hip): clients per fa_pairwise_sqdist launch
 
     def pairwise_sqdist(self, segments: Sequence[Sequence[torch.Tensor]], stream=None,

@@ -16,6 +16,10 @@
  *   fa_centered_sum_sqdist, fa_centered_sum_sqdist_tiled  no reference code here: one pass of centered
  *                       clipping (Karimireddy, He, Jaggi 2021) around a center the caller supplies,
  *                       fused with every client's squared distance to the result; or the distances alone
+ *   fa_sign_vote_sum, fa_sign_vote_sum_tiled  no reference code here (the reference lists it as
+ *                       robust_learning_rate): the robust learning rate of Ozdayi, Kantarcioglu, Gel 2021,
+ *                       the weighted sum fused with a per-coordinate vote of the clients' signs that
+ *                       negates the sum where too few agree
  *   fa_pairwise_sqdist  core/security/defense/krum_defense.py:52-66 (_compute_krum_score's
  *                       compute_euclidean_distance(v_i, v_j) ** 2 for every pair)
  *   fa_pairwise_sqdist_rt  the same for bfloat16 / float16 models (differences in the model dtype)
@@ -195,6 +199,52 @@ int fa_centered_sum_sqdist_tiled(fa_ctx *ctx, int dtype, int32_t num_segments, c
                                  const void *const *d_in, int64_t tile_stride, const void *const *d_center,
                                  const double *coef, void *const *d_out, void *d_stats, void *d_scratch,
                                  size_t scratch_bytes, void *hip_stream);
+
+/*
+ * The robust learning rate (Ozdayi, Kantarcioglu, Gel 2021, "Defending against Backdoors in Federated
+ * Learning with Robust Learning Rate"): the weighted sum of the k clients' updates with, per
+ * coordinate, a vote of the updates' signs -- where fewer than `threshold` net votes agree, the
+ * server's learning rate is negated for that coordinate -- in one read of the inputs from HBM.
+ * d_center non-NULL: the updates are x_i - center (d_center[s]: the center of segment s, a flat
+ * contiguous tensor of seg_numel[s] elements of `dtype`, flat in the tiled entry too, like d_out[s]) and
+ * the result is center + the signed sum; d_center NULL: the inputs are the updates themselves.
+ * Pointer layout d_in[s * k + i], dtypes (F32, BF16, F16, F64; I64: FA_ERR_DTYPE), segment rules, host
+ * tables staged by the library, asynchrony on the caller's stream, the tiled addressing:
+ * fa_centered_sum_sqdist's.  Any k >= 1.  coef: k host doubles (required).  0 <= threshold <= k (else
+ * FA_ERR_INVALID).
+ *
+ * Contract, bit-exact (tests/test_gpu_robust_lr.py).  A = float32 for F32, BF16, F16, float64 for
+ * F64; rnd rounds once to the storage type; nothing is fused; coef is cast to A.  For every element e
+ * of every segment:
+ *   u_i = rnd(x_i[e] - c) with c = center[e];  without a center u_i = x_i[e]
+ *   s_i = +1 if u_i > 0, -1 if u_i < 0, else 0 (+-0 and NaN vote 0, +-Inf vote +-1)
+ *   net = sum_i s_i, an exact integer (every client has one vote; coef plays no part in it)
+ *   t_i = rnd(u_i * (A)coef_i);  acc = t_0;  acc = rnd(acc + t_i) for i = 1 .. k-1 in client order
+ *   if |net| < threshold: acc = -acc (the sign bit alone: exact)
+ *   out[e] = rnd(c + acc);  without a center out[e] = acc
+ * So with threshold 0 and a center, out is fa_centered_sum_sqdist's out for the same inputs and
+ * coefficients, and with threshold 0 and no center it is fa_weighted_sum's FA_MODE_MUL_W result, both
+ * bit for bit, NaNs included.  d_out[s] may be the very pointer d_center[s] (in place: each element is
+ * read and then written by the one lane that owns it); no other overlap of d_out with d_center or d_in
+ * is allowed.
+ *
+ * d_flipped: NULL, or one int64 on the device, to which the call writes the number of elements, over
+ * all segments, with |net| < threshold (an integer: one value, whatever the order of the adds; 0 when
+ * all segments are empty).
+ *
+ * Checked before any HIP call, in this order: ctx; (tiled) tile_stride > 0; k, num_segments, seg_numel,
+ * d_in, d_out; coef; threshold; dtype (I64: FA_ERR_DTYPE); (tiled) tile_stride a multiple of
+ * FA_TILE_BYTES; per non-empty segment its center (when d_center is given), output and input pointers.
+ */
+int fa_sign_vote_sum(fa_ctx *ctx, int dtype, int32_t num_segments, const int64_t *seg_numel, int32_t k,
+                     const void *const *d_in, const void *const *d_center, const double *coef, int32_t threshold,
+                     void *const *d_out, void *d_flipped, void *hip_stream);
+/* The same over tile-interleaved client rows (addressing and tile rules of fa_coord_median_tiled):
+ * out and the count bit for bit fa_sign_vote_sum's over the logical rows. */
+int fa_sign_vote_sum_tiled(fa_ctx *ctx, int dtype, int32_t num_segments, const int64_t *seg_numel, int32_t k,
+                           const void *const *d_in, int64_t tile_stride, const void *const *d_center,
+                           const double *coef, int32_t threshold, void *const *d_out, void *d_flipped,
+                           void *hip_stream);
 
 /*
  * Pairwise squared Euclidean distances of k float32 client vectors (2 <= k <= 128), each given
