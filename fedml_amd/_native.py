@@ -24,13 +24,14 @@ TILE_BYTES = 4096  # FA_TILE_BYTES
 
 F32, BF16, F16, F64, I64 = 0, 1, 2, 3, 4
 MUL_W, MUL_N_DIV_N, SUM = 0, 1, 2
+ADAPT_ADAM, ADAPT_YOGI, ADAPT_ADAGRAD = 0, 1, 2  # FA_ADAPT_* (fa_fedavg_adaptive's rule)
 
 FA_OK, FA_ERR_INVALID, FA_ERR_DTYPE, FA_ERR_HIP, FA_ERR_NOMEM, FA_ERR_COMM = 0, -1, -2, -3, -4, -5
 
 EXPORTED_SYMBOLS = (
     "fa_abi_version", "fa_ctx_create", "fa_ctx_destroy", "fa_weighted_sum",
     "fa_weighted_sum_multi", "fa_weighted_sum_tiled", "fa_weighted_sum_tiled_multi", "fa_weighted_sum_pair", "fa_weighted_sum_pair_multi", "fa_weighted_sum_grouped", "fa_weighted_sum_grouped_tiled",
-    "fa_fedavg_sgd", "fa_fedavg_sgd_tiled", "fa_fedavg_rmsprop", "fa_mix", "fa_mix_tiled", "fa_ctx_set_variant",
+    "fa_fedavg_sgd", "fa_fedavg_sgd_tiled", "fa_fedavg_rmsprop", "fa_fedavg_adaptive", "fa_fedavg_adaptive_tiled", "fa_mix", "fa_mix_tiled", "fa_ctx_set_variant",
     "fa_ctx_set_mix_band", "fa_stream_create_cu_masked", "fa_stream_destroy", "fa_strerror", "fa_last_error",
     "fa_promote_add", "fa_weighted_sum_host", "fa_pushsum", "fa_read_probe",
     "fa_device_alloc_contiguous", "fa_device_free",
@@ -139,6 +140,13 @@ def _declare(L):
     L.fa_fedavg_sgd_tiled.argtypes = [_vp, ctypes.c_int64, ctypes.c_int32, _P_vp, ctypes.c_int64, _P_d, _vp, _vp,
                                       ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                       ctypes.c_int, ctypes.c_int, _vp]
+    _adaptive_tail = [_P_d, _P_vp, _P_vp, _P_vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                      ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int64, _vp]
+    L.fa_fedavg_adaptive.restype = ctypes.c_int
+    L.fa_fedavg_adaptive.argtypes = [_vp, ctypes.c_int32, _P_i64, ctypes.c_int32, _P_vp] + _adaptive_tail
+    L.fa_fedavg_adaptive_tiled.restype = ctypes.c_int
+    L.fa_fedavg_adaptive_tiled.argtypes = [_vp, ctypes.c_int32, _P_i64, ctypes.c_int32, _P_vp,
+                                           ctypes.c_int64] + _adaptive_tail
     L.fa_mix.restype = ctypes.c_int
     L.fa_mix.argtypes = [_vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int32, _P_i32, _P_i32, _P_d,
                          ctypes.c_int32, _P_vp, _P_vp, _P_d, _P_vp, _vp]

@@ -1,5 +1,5 @@
 // elem.h -- the one device copy of the element arithmetic and the storage-type conversions, shared by
-// every kernel family whose results must agree to the bit (fedagg.hip, wsum_dist.hip, signvote.hip, promote.hip,
+// every kernel family whose results must agree to the bit (fedagg.hip, wsum_dist.hip, signvote.hip, fedopt_adaptive.hip, promote.hip,
 // median_common.h, trimmed.hip).  It works on bits and values only: each family keeps its own loads
 // and stores (generic or global address space, temporal or not), which differ on purpose.  Not part
 // of the ABI.

@@ -1,7 +1,8 @@
 // median_common.h -- device helpers shared by the per-column kernels of the robust family
 // (median.hip: coordinate-wise median; trimmed.hip: coordinate-wise trimmed mean; wsum_dist.hip: the
 // fused weighted sum and squared distances): raw global loads, the per-column element access, the
-// order-preserving float key, the segment record, the flat / tile-interleaved column addressing.
+// order-preserving float key, the segment record, the flat / tile-interleaved column addressing, and
+// the slot load of the kernels that walk one 4-KiB slot per client (signvote.hip, fedopt_adaptive.hip).
 // The conversions are elem.h's; the common host path is median_host.h.  Not part of the ABI.
 #pragma once
 
@@ -87,6 +88,38 @@ __device__ __forceinline__ int64_t col_base(int64_t e0, int64_t tstride) {
   return tstride ? (e0 / E) * tstride + (e0 % E) * SZ : e0 * SZ;
 }
 __device__ __forceinline__ const void* at(const void* p, int64_t ub) { return (const char*)p + ub; }
+
+// One client's V elements of this lane, for the kernels whose workgroup owns one 4-KiB slot per
+// client (signvote.hip, fedopt_adaptive.hip).  VEC: one 16-byte load at byte offset off[0]; else
+// element loads at the clamped element indices off[j] (coalesced across the wave: element j of lane l
+// is the slot's element j * kBlock + l).
+template <int DT, bool VEC>
+struct SlotLoad {
+  using T = El<DT>;
+  using A = typename T::A;
+  static constexpr int V = T::V;
+  static constexpr int NR = VEC ? 1 : V;
+  using Raw = typename std::conditional<VEC, u32x4, A>::type;
+
+  int64_t off[NR];
+
+  __device__ void load(Raw (&r)[NR], const void* p) const {
+    if constexpr (VEC) {
+      r[0] = __builtin_nontemporal_load((const __attribute__((address_space(1))) u32x4*)((const char*)p + off[0]));
+    } else {
+#pragma unroll
+      for (int j = 0; j < V; ++j) r[j] = T::from_bits(gld<typename T::S>(p, off[j]));
+    }
+  }
+  __device__ static void get(const Raw (&r)[NR], A (&x)[V]) {
+    if constexpr (VEC) {
+      T::unpack(r[0], x);
+    } else {
+#pragma unroll
+      for (int j = 0; j < V; ++j) x[j] = r[j];
+    }
+  }
+};
 
 // float64 has no MedT (no network runs on it): its element size, and any dtype's element
 // at(p, ub) + lane offset c (elements) widened exactly to double, for the in-order kernels

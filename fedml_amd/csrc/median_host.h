@@ -1,5 +1,5 @@
 // median_host.h -- the host path shared by the C entries that launch over an MSeg table (median.hip,
-// trimmed.hip, wsum_dist.hip, signvote.hip): argument checks, the grid for a given element count per
+// trimmed.hip, wsum_dist.hip, signvote.hip, fedopt_adaptive.hip): argument checks, the grid for a given element count per
 // workgroup, the MSeg + pointer table (and an entry's own payload) in a staging slot, and the launch.
 // An entry checks in this order: col_check_args (NULL context, then the other arguments), its own
 // arguments (the trim; d_center, coef and d_stats; coef and the threshold), col_count (dtype,

@@ -36,38 +36,7 @@ namespace {
 constexpr int kU = 8;   // clients whose loads are in flight together (whole aligned slots)
 constexpr int kUE = 4;  // the same on the element path
 
-// One client's V elements of this lane.  VEC: one 16-byte load at byte offset off[0]; else element
-// loads at the clamped element indices off[j] (coalesced across the wave: element j of lane l is the
-// slot's element j * kBlock + l).
-template <int DT, bool VEC>
-struct SlotLoad {
-  using T = El<DT>;
-  using A = typename T::A;
-  static constexpr int V = T::V;
-  static constexpr int NR = VEC ? 1 : V;
-  using Raw = typename std::conditional<VEC, u32x4, A>::type;
-
-  int64_t off[NR];
-
-  __device__ void load(Raw (&r)[NR], const void* p) const {
-    if constexpr (VEC) {
-      r[0] = __builtin_nontemporal_load((const __attribute__((address_space(1))) u32x4*)((const char*)p + off[0]));
-    } else {
-#pragma unroll
-      for (int j = 0; j < V; ++j) r[j] = T::from_bits(gld<typename T::S>(p, off[j]));
-    }
-  }
-  __device__ static void get(const Raw (&r)[NR], A (&x)[V]) {
-    if constexpr (VEC) {
-      T::unpack(r[0], x);
-    } else {
-#pragma unroll
-      for (int j = 0; j < V; ++j) x[j] = r[j];
-    }
-  }
-};
-
-// One client into the lane's V sums and votes.
+// One client into the lane's V sums and votes.  (The slot's loads: SlotLoad, median_common.h.)
 template <int DT, bool CEN>
 __device__ __forceinline__ void sv_consume(const typename El<DT>::A (&x)[El<DT>::V],
                                            const typename El<DT>::A (&cen)[El<DT>::V], typename El<DT>::A c,

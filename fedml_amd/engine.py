@@ -521,6 +521,86 @@ class AggEngine:
             float(weight_decay), int(bool(nesterov)), int(bool(first_step)), self._stream(stream))
         N.check(rc, "fa_fedavg_sgd_tiled")
 
+    def _adaptive_state(self, what: str, params, m, v, beta1: float):
+        """The parameters and state of the adaptive step: float32, contiguous, on this device, state
+        shaped like its parameter; ``m`` is None exactly when beta1 == 0.  Returns the three pointer
+        tables (the first moments' is None without momentum)."""
+        if (m is None) != (float(beta1) == 0.0):
+            raise ValueError(f"{what}: the first moments are None exactly when beta1 == 0 (beta1 {beta1})")
+        if len(v) != len(params) or (m is not None and len(m) != len(params)):
+            raise ValueError(f"{what}: one first and one second moment per parameter")
+        for s, p in enumerate(params):
+            state = [(p, "parameter"), (v[s], "second moment")] + ([(m[s], "first moment")] if m is not None else [])
+            for t, name in state:
+                if t.dtype != torch.float32 or t.shape != p.shape:
+                    raise TypeError(f"{what}: {name} {s} must be float32 of shape {tuple(p.shape)}")
+                _require_device(t, self.device, f"{name} {s}")
+
+        def table(ts):
+            return N.ptr_array([t.data_ptr() for t in ts])
+        return table(params), None if m is None else table(m), table(v)
+
+    @staticmethod
+    def _adaptive_scalars(what: str, rule, lr, beta1, beta2, eps, weight_decay, bias_correction, step):
+        if rule not in (N.ADAPT_ADAM, N.ADAPT_YOGI, N.ADAPT_ADAGRAD):
+            raise ValueError(f"{what}: rule must be ADAPT_ADAM, ADAPT_YOGI or ADAPT_ADAGRAD (got {rule!r})")
+        if not (0.0 <= beta1 < 1.0 and 0.0 <= beta2 < 1.0 and eps >= 0.0):
+            raise ValueError(f"{what}: need 0 <= beta1 < 1, 0 <= beta2 < 1 and eps >= 0")
+        if isinstance(step, bool) or int(step) != step or step < 1:
+            raise ValueError(f"{what}: step must be an integer >= 1 (got {step!r})")
+        return (int(rule), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+                int(bool(bias_correction)), int(step))
+
+    def fedavg_adaptive(self, segments: Sequence[Sequence[torch.Tensor]], coef: Sequence[float],
+                        params: Sequence[torch.Tensor], m: Optional[Sequence[torch.Tensor]],
+                        v: Sequence[torch.Tensor], rule: int, lr: float, beta1: float, beta2: float, eps: float,
+                        weight_decay: float = 0.0, bias_correction: bool = False, step: int = 1, stream=None) -> None:
+        """FedAvg + an adaptive server step in one pass (fa_fedavg_adaptive; the contract:
+        include/fedagg.h): ``rule`` = N.ADAPT_ADAM / ADAPT_YOGI / ADAPT_ADAGRAD.  params, the first
+        moments ``m`` (None exactly when beta1 == 0) and the second moments ``v`` -- fp32, contiguous,
+        on this device -- are updated in place; the state is always read, so the caller initialises it."""
+        what = "fedavg_adaptive"
+        k = len(segments[0]) if segments else 0
+        if k == 0:
+            raise ValueError(f"{what}: no client tensors")
+        if len(coef) != k or len(params) != len(segments):
+            raise ValueError(f"{what}: one coefficient per client and one parameter per segment")
+        scalars = self._adaptive_scalars(what, rule, lr, beta1, beta2, eps, weight_decay, bias_correction, step)
+        pptr, mptr, vptr = self._adaptive_state(what, params, m, v, beta1)
+        in_ptrs = []
+        for s, (seg, p) in enumerate(zip(segments, params)):
+            if len(seg) != k:
+                raise ValueError(f"segment {s}: {len(seg)} clients, expected {k}")
+            for i, t in enumerate(seg):
+                if t.dtype != torch.float32 or t.shape != p.shape:
+                    raise ValueError(f"segment {s} client {i}: must be float32 of shape {tuple(p.shape)}")
+                _require_device(t, self.device, f"segment {s} client {i}")
+                in_ptrs.append(t.data_ptr())
+        rc = self._lib.fa_fedavg_adaptive(
+            self._ctx, len(params), N.i64_array([p.numel() for p in params]), k, N.ptr_array(in_ptrs),
+            N.f64_array(coef), pptr, mptr, vptr, *scalars, self._stream(stream))
+        N.check(rc, "fa_fedavg_adaptive")
+
+    def fedavg_adaptive_tiled(self, buf: torch.Tensor, rows: Sequence[int], coef: Sequence[float],
+                              param: torch.Tensor, m: Optional[torch.Tensor], v: torch.Tensor, rule: int, lr: float,
+                              beta1: float, beta2: float, eps: float, weight_decay: float = 0.0,
+                              bias_correction: bool = False, step: int = 1, stream=None) -> None:
+        """``fedavg_adaptive`` of ONE flat fp32 parameter over rows of a tile-interleaved arena group
+        ``buf`` [tiles, capacity, E] (fa_fedavg_adaptive_tiled): the same bits as over the logical rows.
+        ``param``, ``m`` (None exactly when beta1 == 0) and ``v`` are flat and updated in place."""
+        what = "fedavg_adaptive_tiled"
+        if buf.dtype != torch.float32:
+            raise TypeError(f"{what}: float32 only")
+        n, ptrs, stride = self._tiled_args(buf, rows, 0, param.numel(), what)
+        if len(coef) != len(rows):
+            raise ValueError(f"{what}: one coefficient per row")
+        scalars = self._adaptive_scalars(what, rule, lr, beta1, beta2, eps, weight_decay, bias_correction, step)
+        pptr, mptr, vptr = self._adaptive_state(what, [param], None if m is None else [m], [v], beta1)
+        rc = self._lib.fa_fedavg_adaptive_tiled(
+            self._ctx, 1, N.i64_array([n]), len(rows), ptrs, stride, N.f64_array(coef), pptr, mptr, vptr, *scalars,
+            self._stream(stream))
+        N.check(rc, "fa_fedavg_adaptive_tiled")
+
     def weighted_sum_table(self, dtype_code: int, mode: int, seg_numel: torch.Tensor, k: int,
                            in_ptrs: torch.Tensor, out_ptrs: torch.Tensor, coef: Optional[Sequence[float]] = None,
                            divisor: float = 1.0, stream=None) -> None:

@@ -17,7 +17,28 @@ torch.optim.SGD; bit-exact) and ``rmsprop`` (torch.optim.RMSprop defaults alpha 
 centered = False; within 1e-6 relative -- the reference's CPU sqrt is MKL-VML, not correctly
 rounded).  The reference instantiates its optimizer with ``lr=`` and ``momentum=`` for any name
 (FedOptAggregator.py:49-54), so those two are the only ones it can construct (Adam, Adagrad, ...
-raise TypeError there); others raise NotImplementedError here.
+raise TypeError there).
+
+The adaptive server steps (``fa_fedavg_adaptive``, one launch per round; bit-exact to the per-op
+contract in include/fedagg.h, within 1e-6 normwise of torch.optim where torch has the optimizer):
+
+=============  =======  ==============================================================  ================
+name           rule     defaults                                                        state at round 1
+=============  =======  ==============================================================  ================
+``adam``       ADAM     beta1 0.9, beta2 0.999, eps 1e-8, bias correction on            m = v = 0
+                        (torch.optim.Adam)
+``adagrad``    ADAGRAD  beta1 0 (no m), eps 1e-10, no bias correction                   v = 0
+                        (torch.optim.Adagrad, lr_decay 0)
+``fedadam``    ADAM     Reddi et al. (ICLR 2021) Alg. 2: beta1 0.9, beta2 0.99,         m = 0, v = tau^2
+                        tau 1e-3, no bias correction
+``fedyogi``    YOGI     the same                                                        the same
+``fedadagrad`` ADAGRAD  beta1 0.9, tau 1e-3                                             m = 0, v = tau^2
+=============  =======  ==============================================================  ================
+
+Config: ``server_beta1``, ``server_beta2``, ``server_eps`` (= tau; torch's eps for ``adam`` and
+``adagrad``), ``server_weight_decay``.  Reddi's update x + eta m / (sqrt(v) + tau) with Delta = avg - x
+is the contract's g = p - avg and p - ... .  The aggregator owns m, v and the round counter (``step``
+= rounds aggregated so far + 1).  Other names raise NotImplementedError.
 """
 from __future__ import annotations
 
@@ -27,8 +48,18 @@ from typing import Dict, List
 
 import torch
 
+from ..._native import ADAPT_ADAGRAD, ADAPT_ADAM, ADAPT_YOGI
 from ...engine import get_engine
 from ...ml.aggregator.state_dict_agg import MUL_W, aggregate
+
+# name: (rule, beta1, beta2, eps or tau, bias correction, v starts at tau^2); beta2 is unused by ADAGRAD
+ADAPTIVE = {
+    "adam": (ADAPT_ADAM, 0.9, 0.999, 1e-8, True, False),
+    "adagrad": (ADAPT_ADAGRAD, 0.0, 0.0, 1e-10, False, False),
+    "fedadam": (ADAPT_ADAM, 0.9, 0.99, 1e-3, False, True),
+    "fedyogi": (ADAPT_YOGI, 0.9, 0.99, 1e-3, False, True),
+    "fedadagrad": (ADAPT_ADAGRAD, 0.9, 0.0, 1e-3, False, True),
+}
 
 
 class FedOptAggregator:
@@ -37,10 +68,22 @@ class FedOptAggregator:
         self.aggregator = server_aggregator
         self.args = args
         name = str(getattr(args, "server_optimizer", "sgd")).lower()
-        if name not in ("sgd", "rmsprop"):
-            raise NotImplementedError(f"server_optimizer={name!r}: the fused FedOpt step implements 'sgd' and "
-                                      "'rmsprop' (the optimizers the reference can construct with momentum=)")
+        if name not in ("sgd", "rmsprop") and name not in ADAPTIVE:
+            raise NotImplementedError(f"server_optimizer={name!r}: the fused FedOpt step implements 'sgd', 'rmsprop' "
+                                      f"(the optimizers the reference can construct with momentum=) and "
+                                      f"{', '.join(repr(a) for a in ADAPTIVE)}")
         self.opt_name = name
+        if name in ADAPTIVE:
+            self.rule, beta1, beta2, eps, self.bias_correction, reddi = ADAPTIVE[name]
+
+            def conf(key, default):
+                given = getattr(args, key, None)
+                return default if given is None else float(given)
+            self.beta1, self.beta2, self.eps = conf("server_beta1", beta1), conf("server_beta2", beta2), conf("server_eps", eps)
+            self.v0 = self.eps * self.eps if reddi else 0.0  # Reddi's v_-1 = tau^2; torch starts at 0
+        self.exp_avg: Dict[str, torch.Tensor] = {}     # adaptive state: first moment m
+        self.exp_avg_sq: Dict[str, torch.Tensor] = {}  # and second moment v
+        self.rounds = 0  # rounds aggregated so far; the adaptive step's `step` is rounds + 1
         self.lr = float(args.server_lr)
         self.momentum = float(getattr(args, "server_momentum", 0.0) or 0.0)
         self.dampening = float(getattr(args, "server_dampening", 0.0) or 0.0)
@@ -86,6 +129,41 @@ class FedOptAggregator:
         # global parameters: fused FedAvg + pseudo-gradient + SGD step, in place
         gparams = [p.data if on_gpu else p.data.to(eng.device) for _, p in named]
         segs = [[d[k].to(eng.device).contiguous() for d in dicts] for k, _ in named]
+        step = self._adaptive_step if self.opt_name in ADAPTIVE else self._sgd_step
+        step(eng, named, segs, w, gparams)
+        self.rounds += 1
+        if not on_gpu:
+            with torch.no_grad():
+                for (_, p), g in zip(named, gparams):
+                    p.data.copy_(g.cpu())
+        # buffers (and frozen parameters, which the reference leaves at their old value)
+        sd = model.state_dict()
+        rest = [k for k in dicts[0].keys() if k not in all_params]
+        if rest:
+            avg = aggregate([{k: d[k] for k in rest} for d in dicts], MUL_W, w)
+            with torch.no_grad():
+                for k in rest:
+                    sd[k].copy_(avg[k])  # load_state_dict semantics: cast into the buffer dtype
+        logging.info("aggregate time cost: %.6f s", time.time() - t0)
+        return self.get_global_model_params()
+
+    def _adaptive_step(self, eng, named, segs, w, gparams):
+        """One fa_fedavg_adaptive launch over every parameter.  A parameter first seen in a later round
+        gets fresh state (m = 0, v = v0) but the bias-correction step of the aggregator's round counter,
+        which every parameter of the launch shares."""
+        if not named:  # every parameter frozen
+            return
+        for (k, _), g in zip(named, gparams):
+            if k not in self.exp_avg_sq:
+                self.exp_avg_sq[k] = torch.full_like(g, self.v0)
+                if self.beta1 != 0.0:
+                    self.exp_avg[k] = torch.zeros_like(g)
+        m = [self.exp_avg[k] for k, _ in named] if self.beta1 != 0.0 else None
+        eng.fedavg_adaptive(segs, w, gparams, m, [self.exp_avg_sq[k] for k, _ in named], self.rule, self.lr,
+                            self.beta1, self.beta2, self.eps, weight_decay=self.weight_decay,
+                            bias_correction=self.bias_correction, step=self.rounds + 1)
+
+    def _sgd_step(self, eng, named, segs, w, gparams):
         first = [k not in (self.square_avg if self.opt_name == "rmsprop" else self.momentum_buffer) for k, _ in named]
         rms = self.opt_name == "rmsprop"
         for (k, p), g in zip(named, gparams):
@@ -106,17 +184,3 @@ class FedOptAggregator:
                 eng.fedavg_sgd([segs[j] for j in idx], w, [gparams[j] for j in idx], mbufs,
                                self.lr, self.momentum, self.dampening, self.weight_decay, self.nesterov,
                                first_step=flag)
-        if not on_gpu:
-            with torch.no_grad():
-                for (_, p), g in zip(named, gparams):
-                    p.data.copy_(g.cpu())
-        # buffers (and frozen parameters, which the reference leaves at their old value)
-        sd = model.state_dict()
-        rest = [k for k in dicts[0].keys() if k not in all_params]
-        if rest:
-            avg = aggregate([{k: d[k] for k in rest} for d in dicts], MUL_W, w)
-            with torch.no_grad():
-                for k in rest:
-                    sd[k].copy_(avg[k])  # load_state_dict semantics: cast into the buffer dtype
-        logging.info("aggregate time cost: %.6f s", time.time() - t0)
-        return self.get_global_model_params()

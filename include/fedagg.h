@@ -223,6 +223,59 @@ int fa_fedavg_sgd_tiled(fa_ctx *ctx, int64_t n, int32_t k, const void *const *d_
                         int nesterov, int first_step, void *hip_stream);
 
 /*
+ * The adaptive FedOpt server steps fused into the FedAvg pass: FedAdam, FedYogi and FedAdagrad of
+ * Reddi et al., "Adaptive Federated Optimization" (ICLR 2021, Alg. 2), and torch.optim.Adam /
+ * torch.optim.Adagrad (the reference's single-process FedOpt builds its optimizer with lr= alone).
+ * Parameters, state and clients are float32; segments are parameter tensors; d_in[s * k + i] as in
+ * fa_sign_vote_sum (fedagg_robust.h), the tiled entry with the addressing of fa_coord_median_tiled.
+ * d_param[s], d_m[s] (first moment) and d_v[s] (second moment) are always flat and all three are
+ * updated IN PLACE.  The state is always read: the caller initialises it (zeros, or tau^2 for
+ * Reddi's v_-1); there is no first_step.  d_m is NULL exactly when beta1 == 0: no momentum, the
+ * numerator is g (torch.optim.Adagrad).  p, m and v must not overlap each other or any input.
+ * Asynchronous on hip_stream.
+ *
+ * Contract (bit-exact): float32 throughout, every op rounded once (rnd), NOTHING fused; host scalars
+ * are cast double -> float once, 1 - beta is formed in double and then cast.  Per element, with p,
+ * m, v the stored values:
+ *   avg = fa_weighted_sum FA_MODE_MUL_W arithmetic (clients in order, t_i = rnd(x_i * (float)coef_i),
+ *         ordered sum)
+ *   g   = rnd(p - avg);            if weight_decay != 0: g = rnd(g + rnd(p * wd))
+ *   g2  = rnd(g * g)
+ *   ADAM:    v = rnd(rnd(v * b2) + rnd(g2 * (float)(1 - beta2)))
+ *   YOGI:    s = sign(rnd(v - g2)) in {-1, 0, +1} (NaN: 0);
+ *            v = rnd(v - rnd(rnd((float)(1 - beta2) * g2) * s))
+ *   ADAGRAD: v = rnd(v + g2)                         (beta2 ignored)
+ *   beta1 != 0: m = rnd(rnd(m * b1) + rnd(g * (float)(1 - beta1)));  num = m      else num = g
+ *   c2   = bias_correction ? (float)sqrt(1 - beta2^step) : 1.0f     (computed in double on the host)
+ *   step_size = (float)(bias_correction ? lr / (1 - beta1^step) : lr)
+ *   den  = rnd(rnd(sqrtf_cr(v) / c2) + (float)eps)    sqrtf_cr: correctly rounded
+ *   p    = rnd(p - rnd(step_size * rnd(num / den)))
+ * The float32 division is correctly rounded; the square root is the float64 sqrt rounded to float32
+ * (as fa_fedavg_rmsprop computes it).  Elements where a NaN or Inf enters give NaN or Inf where this
+ * restatement does; NaN bits are unspecified.  Reddi's update x + eta m / (sqrt(v) + tau) with
+ * Delta = avg - x is this one with g = -Delta, eps = tau and no bias correction.  torch's own op
+ * sequence (lerp, addcdiv) rounds differently: within 1e-6 normwise of torch.optim, not bit-exact.
+ *
+ * Checked before any HIP call, in this order: ctx; (tiled) tile_stride > 0; k, num_segments,
+ * seg_numel, d_in, d_param; coef; d_v; d_m (NULL iff beta1 == 0); rule; 0 <= beta1 < 1,
+ * 0 <= beta2 < 1, eps >= 0, step >= 1; (tiled) tile_stride a multiple of FA_TILE_BYTES; per non-empty
+ * segment its parameter, client and state pointers.  Failures return FA_ERR_INVALID; all segments
+ * empty is FA_OK with nothing launched.
+ */
+enum { FA_ADAPT_ADAM = 0, FA_ADAPT_YOGI = 1, FA_ADAPT_ADAGRAD = 2 };
+
+int fa_fedavg_adaptive(fa_ctx *ctx, int32_t num_segments, const int64_t *seg_numel, int32_t k,
+                       const void *const *d_in, const double *coef, void *const *d_param,
+                       void *const *d_m, void *const *d_v, int rule, double lr, double beta1,
+                       double beta2, double eps, double weight_decay, int bias_correction,
+                       int64_t step, void *hip_stream);
+int fa_fedavg_adaptive_tiled(fa_ctx *ctx, int32_t num_segments, const int64_t *seg_numel, int32_t k,
+                             const void *const *d_in, int64_t tile_stride, const double *coef,
+                             void *const *d_param, void *const *d_m, void *const *d_v, int rule,
+                             double lr, double beta1, double beta2, double eps, double weight_decay,
+                             int bias_correction, int64_t step, void *hip_stream);
+
+/*
  * Mixing / gossip: for every row r < rows, with CSR entries j in [row_ptr[r], row_ptr[r+1]):
  *   d_out[r][e] = ordered MUL_W reduction of d_in[cols[j]][e] * vals[j]   (entry order = CSR order)
  *   if post_scale: d_out2[r][e] = op(d_out[r][e] * post_scale[r])         (PushSum z = x / omega)
