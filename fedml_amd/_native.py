@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = (
     "fa_weighted_sum_sqdist", "fa_weighted_sum_sqdist_tiled", "fa_weighted_sum_sqdist_scratch_bytes", "fa_pairwise_sqdist", "fa_pairwise_sqdist_rt", "fa_pairwise_sqdist_scratch_bytes",
     "fa_centered_sum_sqdist", "fa_centered_sum_sqdist_tiled",
     "fa_sign_vote_sum", "fa_sign_vote_sum_tiled",
+    "fa_pairwise_dot", "fa_pairwise_dot_tiled", "fa_pairwise_dot_scratch_bytes",
     "fa_pairwise_sqdist_gram", "fa_pairwise_sqdist_gram_scratch_bytes", "fa_pairwise_sqdist_gram_limit",
     # include/fedagg_comm.h
     "fa_comm_unique_id", "fa_comm_init", "fa_comm_wrap", "fa_comm_destroy", "fa_comm_size", "fa_local_out_dtype",
@@ -203,6 +204,14 @@ def _declare(L):
     L.fa_sign_vote_sum_tiled.restype = ctypes.c_int
     L.fa_sign_vote_sum_tiled.argtypes = [_vp, ctypes.c_int, ctypes.c_int32, _P_i64, ctypes.c_int32, _P_vp,
                                          ctypes.c_int64, _P_vp, _P_d, ctypes.c_int32, _P_vp, _vp, _vp]
+    L.fa_pairwise_dot.restype = ctypes.c_int
+    L.fa_pairwise_dot.argtypes = [_vp, ctypes.c_int, ctypes.c_int32, _P_i64, ctypes.c_int32, _P_vp, _P_vp, _P_vp, _vp,
+                                  _vp, ctypes.c_size_t, _vp]
+    L.fa_pairwise_dot_tiled.restype = ctypes.c_int
+    L.fa_pairwise_dot_tiled.argtypes = [_vp, ctypes.c_int, ctypes.c_int32, _P_i64, ctypes.c_int32, _P_vp,
+                                        ctypes.c_int64, _P_vp, _P_vp, _vp, _vp, ctypes.c_size_t, _vp]
+    L.fa_pairwise_dot_scratch_bytes.restype = ctypes.c_size_t
+    L.fa_pairwise_dot_scratch_bytes.argtypes = [ctypes.c_int32, _P_i64, ctypes.c_int32]
     L.fa_weighted_sum_sqdist_scratch_bytes.restype = ctypes.c_size_t
     L.fa_weighted_sum_sqdist_scratch_bytes.argtypes = [ctypes.c_int32, _P_i64, ctypes.c_int32]
     L.fa_pairwise_sqdist.restype = ctypes.c_int

@@ -726,6 +726,45 @@ class ClientArena:
                         elements=sum(kn for _, _, _, kn in self.layout.where.values()))
         return self.layout.carve(outs)
 
+    def pairwise_dot(self, center: Optional[Dict[torch.dtype, torch.Tensor]] = None,
+                     hists: Optional[Dict[torch.dtype, torch.Tensor]] = None,
+                     clients: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """FoolsGold's pass (include/fedagg_robust.h, fa_pairwise_dot) over the given client rows
+        (default: all): the K x K float64 device matrix of the inner products of y_i, with u_i = x_i -
+        center rounded in the dtype (``center``: dtype -> flat device tensor of the group's elements in
+        the layout's order, only read; None: u_i = x_i) and y_i = u_i, or with ``hists`` (dtype -> a
+        contiguous [K, group elements] device tensor of the group's dtype, row i the history of
+        clients[i]) every history updated in place, h_i += u_i, and y_i the stored h_i.  ONE launch per
+        dtype group -- tiled arenas through the tiled entry, client-major arenas over the row views --
+        and the groups' matrices added in the order of ``self.bufs`` (inner products add across
+        groups).  Float groups only; at most 128 rows."""
+        rows = list(range(self.capacity)) if clients is None else list(clients)
+        if not rows:
+            raise ValueError("fools_gold: no client rows")
+        if any(dt not in (torch.float32, torch.bfloat16, torch.float16, torch.float64) for dt in self.bufs):
+            raise TypeError("fools_gold: the arena holds a non-float dtype group")
+        for what, given, shape in (("center", center, lambda n: (n,)), ("hists", hists, lambda n: (len(rows), n))):
+            if given is None:
+                continue
+            for dt in self.bufs:
+                t = given.get(dt)
+                want = shape(self.layout.group_numel[dt])
+                if t is None or t.dtype != dt or tuple(t.shape) != want or not t.is_contiguous():
+                    raise ValueError(f"fools_gold: {what}[{dt}] must be a contiguous {dt} tensor of shape {want}")
+        self._wait_ingest()
+        total = None
+        for dt, buf in self.bufs.items():
+            n = self.layout.group_numel[dt]
+            c = center[dt] if center is not None else None
+            hs = list(hists[dt].unbind(0)) if hists is not None else None
+            if self.tiled:
+                g = self.engine.pairwise_dot_tiled(buf, rows, c, hs, n=n)
+            else:
+                g = self.engine.pairwise_dot([[buf[i][:n] for i in rows]], None if c is None else [c],
+                                             None if hs is None else [hs])
+            total = g if total is None else total + g
+        return total
+
     def _pair_groups(self) -> Optional[torch.dtype]:
         """The float dtype when the arena holds exactly one float group and one int64 group."""
         dts = list(self.bufs)

@@ -7,7 +7,8 @@ MI355X engine (``FedMLAggOperator.agg``).
 
 The reference's hooks also drive its DP / attack / defense / contribution subsystems
 (core/dp, core/security, core/contribution).  Defenses that ARE alternative aggregations --
-krum / multikrum, trimmed_mean, wise_median (coordinate-wise median) -- run here through
+krum / multikrum, trimmed_mean, wise_median (coordinate-wise median) and the others FedMLDefender
+lists, fools_gold (client weights before aggregation) among them -- run here through
 ``FedMLDefender`` on the HIP engine, with the reference's hook order.  DP, attacks, contribution
 assessment and the other defenses are outside this engine's scope: the hooks pass data through
 untouched when they are off (the default), and raise NotImplementedError if a config turns one on.
@@ -60,7 +61,8 @@ class ServerAggregator(ABC):
 
     def on_before_aggregation(self, raw_client_model_or_grad_list: List[Tuple[float, OrderedDict]]):
         """Reference :42-65: before-aggregation defenses (krum, multikrum, trimmed_mean) select the
-        clients; otherwise the identity."""
+        clients, and fools_gold drops or down-weights them (its center is the global model passed
+        here); otherwise the identity."""
         client_idxs = [i for i in range(len(raw_client_model_or_grad_list))]
         d = FedMLDefender.get_instance()
         if d.is_defense_enabled():

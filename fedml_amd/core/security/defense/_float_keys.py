@@ -1,5 +1,5 @@
 """The scaffold shared by the defenses that run one engine operator over every floating-point key of
-the clients' dicts (coordinate_trimmed_mean_defense.py, geometric_median_defense.py, centered_clipping_defense.py, bulyan_defense.py, robust_lr_defense.py): which keys take
+the clients' dicts (coordinate_trimmed_mean_defense.py, geometric_median_defense.py, centered_clipping_defense.py, bulyan_defense.py, robust_lr_defense.py; fools_gold_defense.py takes the engine and the per-dtype segments): which keys take
 part, the resident-arena form, the per-dtype segments of the engine form, and the way back to a dict.
 """
 from __future__ import annotations
@@ -13,6 +13,50 @@ from ....arena import resident_rows
 from ....engine import get_engine
 
 _NATIVE = (torch.float32, torch.bfloat16, torch.float16, torch.float64)
+
+
+def engine_of(grads, keys):
+    """(device, engine): the device of the first CUDA tensor among the clients' ``keys`` (None: CPU
+    dicts) and that device's engine (the default device's for CPU dicts)."""
+    dev = next((g[k].device for g in grads for k in keys if g[k].is_cuda), None)
+    return dev, get_engine(dev.index if dev is not None else None)
+
+
+def center_keys(name: str, first, center: dict, keys) -> "OrderedDict":
+    """The center's tensor of every one of ``keys``, checked key by key against client 0's dict
+    ``first`` (present, a tensor, the same dtype and shape); ValueErrors start with ``name``."""
+    cen = OrderedDict()
+    for key in keys:
+        if key not in center:
+            raise ValueError(f"{name}: the center lacks key {key!r}")
+        c = center[key]
+        if not torch.is_tensor(c) or c.dtype != first[key].dtype or c.shape != first[key].shape:
+            raise ValueError(f"{name}: the center's key {key!r} differs in dtype or shape from the clients'")
+        cen[key] = c
+    return cen
+
+
+def dtype_segments(name: str, grads, keys, eng) -> "OrderedDict":
+    """dtype -> (keys, segs) over ``keys`` in the order of their first appearance: segs[key][client] the
+    clients' flat contiguous tensors on the engine's device.  A key whose dtype or shape differs between
+    clients is a ValueError that starts with ``name``."""
+    first = grads[0]
+    by_dt = OrderedDict()
+    for k in keys:
+        by_dt.setdefault(first[k].dtype, []).append(k)
+    groups = OrderedDict()
+    for dt, ks in by_dt.items():
+        segs = []
+        for k in ks:
+            col = []
+            for g in grads:
+                t = g[k]
+                if t.dtype != dt or t.shape != first[k].shape:
+                    raise ValueError(f"{name}: key {k!r} differs in dtype or shape between clients")
+                col.append(t.to(eng.device).contiguous().reshape(-1))
+            segs.append(col)
+        groups[dt] = (ks, segs)
+    return groups
 
 
 def defend_float_keys(name: str, config, raw_client_grad_list: List[Tuple[float, OrderedDict]],
@@ -37,22 +81,10 @@ def defend_float_keys(name: str, config, raw_client_grad_list: List[Tuple[float,
     if hit is not None and all(dt in _NATIVE for dt in hit[0].bufs):
         result.update(on_arena(*hit))
     elif fkeys:
-        dev = next((g[k].device for g in grads for k in fkeys if g[k].is_cuda), None)
-        eng = get_engine(dev.index if dev is not None else None)
-        groups = OrderedDict()  # dtype -> keys
-        for k in fkeys:
-            groups.setdefault(first[k].dtype, []).append(k)
+        dev, eng = engine_of(grads, fkeys)
+        groups = dtype_segments(name, grads, fkeys, eng)  # dtype -> (keys, segs)
         work, vecs = [], []
-        for dt, keys in groups.items():
-            segs = []
-            for k in keys:
-                col = []
-                for g in grads:
-                    t = g[k]
-                    if t.dtype != dt or t.shape != first[k].shape:
-                        raise ValueError(f"{name}: key {k!r} differs in dtype or shape between clients")
-                    col.append(t.to(eng.device).contiguous().reshape(-1))
-                segs.append(col)
+        for dt, (keys, segs) in groups.items():
             vec = torch.empty(sum(c[0].numel() for c in segs), dtype=dt, device=eng.device)
             outs, pos = [], 0
             for c in segs:
@@ -61,7 +93,7 @@ def defend_float_keys(name: str, config, raw_client_grad_list: List[Tuple[float,
             work.append((segs, outs))
             vecs.append(vec)
         on_engine(eng, work)
-        for keys, vec in zip(groups.values(), vecs):
+        for (keys, _), vec in zip(groups.values(), vecs):
             if dev is None:
                 vec = vec.cpu()  # CPU dicts in, CPU tensors out (the copy waits for the launches)
             pos = 0

@@ -32,7 +32,7 @@ from typing import Any, Callable, List, Tuple
 import torch
 
 from ....arena import sign_vote_coef
-from ._float_keys import _NATIVE, defend_float_keys
+from ._float_keys import _NATIVE, center_keys, defend_float_keys
 
 
 class RobustLearningRateDefense(object):
@@ -60,17 +60,7 @@ class RobustLearningRateDefense(object):
     @staticmethod
     def _center_keys(first: OrderedDict, center: dict) -> "OrderedDict[str, torch.Tensor]":
         """The center's tensor of every float key of client 0's dict, checked against it."""
-        cen = OrderedDict()
-        for key, v in first.items():
-            if v.dtype not in _NATIVE:
-                continue
-            if key not in center:
-                raise ValueError(f"robust_lr: the center lacks key {key!r}")
-            c = center[key]
-            if not torch.is_tensor(c) or c.dtype != v.dtype or c.shape != v.shape:
-                raise ValueError(f"robust_lr: the center's key {key!r} differs in dtype or shape from the clients'")
-            cen[key] = c
-        return cen
+        return center_keys("robust_lr", first, center, [key for key, v in first.items() if v.dtype in _NATIVE])
 
     def defend_on_aggregation(self, raw_client_grad_list: List[Tuple[float, OrderedDict]],
                               base_aggregation_func: Callable = None, extra_auxiliary_info: Any = None):

@@ -13,9 +13,12 @@ fedagg_robust.h and is not pinned to a reference fixture) and robust_lr (the rob
 Ozdayi et al. 2021 against backdoors: per coordinate the clients' updates vote with their signs and
 the server's learning rate is negated where fewer than robust_lr_threshold net votes agree; config
 robust_lr_threshold (required), robust_lr_server_lr, robust_lr_center; the reference's own
-robust_learning_rate name stays unserved).  Same dispatch
+robust_learning_rate name stays unserved) and fools_gold (FoolsGold of Fung et al. 2018 against sybils:
+before aggregation, every client's update is added into a running history and clients whose histories
+point the same way are down-weighted or dropped; config fools_gold_use_memory, fools_gold_confidence,
+fools_gold_center; the reference's own foolsgold name stays unserved).  Same dispatch
 (which defenses act before / on / after aggregation) and the same entry points; the per-element work
-runs in the HIP kernels (fedml_amd/csrc/median.hip, trimmed.hip, wsum_dist.hip, signvote.hip, robust.hip).  Other
+runs in the HIP kernels (fedml_amd/csrc/median.hip, trimmed.hip, wsum_dist.hip, signvote.hip, pairdot.hip, robust.hip).  Other
 defense types of the reference are outside the aggregation path and raise NotImplementedError when
 configured.
 """
@@ -26,13 +29,14 @@ from collections import OrderedDict
 from typing import Any, Callable, List, Tuple
 
 from .constants import (DEFENSE_BULYAN, DEFENSE_CENTERED_CLIPPING, DEFENSE_COORD_TRIMMED_MEAN,
-                        DEFENSE_GEOMETRIC_MEDIAN, DEFENSE_KRUM, DEFENSE_MULTIKRUM, DEFENSE_ROBUST_LR,
+                        DEFENSE_FOOLS_GOLD, DEFENSE_GEOMETRIC_MEDIAN, DEFENSE_KRUM, DEFENSE_MULTIKRUM, DEFENSE_ROBUST_LR,
                         DEFENSE_TRIMMED_MEAN, DEFENSE_WISE_MEDIAN)
 from .defense.bulyan_defense import BulyanDefense
 from .defense.centered_clipping_defense import CenteredClippingDefense
 from .defense.coordinate_trimmed_mean_defense import CoordinateTrimmedMeanDefense
 from .defense.coordinate_wise_median_defense import CoordinateWiseMedianDefense
 from .defense.coordinate_wise_trimmed_mean_defense import CoordinateWiseTrimmedMeanDefense
+from .defense.fools_gold_defense import FoolsGoldDefense
 from .defense.geometric_median_defense import GeometricMedianDefense
 from .defense.krum_defense import KrumDefense
 from .defense.robust_lr_defense import RobustLearningRateDefense
@@ -74,11 +78,13 @@ class FedMLDefender:
                 self.defender = BulyanDefense(args)
             elif self.defense_type == DEFENSE_ROBUST_LR:
                 self.defender = RobustLearningRateDefense(args)
+            elif self.defense_type == DEFENSE_FOOLS_GOLD:
+                self.defender = FoolsGoldDefense(args)
             else:
                 raise NotImplementedError(
                     f"defense_type {self.defense_type!r} is not served by the MI355X engine "
                     f"(supported: krum, multikrum, trimmed_mean, wise_median, coordinate_trimmed_mean, "
-                    f"geometric_median, centered_clipping, bulyan, robust_lr)")
+                    f"geometric_median, centered_clipping, bulyan, robust_lr, fools_gold)")
         else:
             self.is_enabled = False
             self.defense_type = None
@@ -97,7 +103,7 @@ class FedMLDefender:
 
     def is_defense_before_aggregation(self):
         return self.is_defense_enabled() and self.defense_type in [DEFENSE_KRUM, DEFENSE_MULTIKRUM,
-                                                                   DEFENSE_TRIMMED_MEAN]
+                                                                   DEFENSE_TRIMMED_MEAN, DEFENSE_FOOLS_GOLD]
 
     def is_defense_after_aggregation(self):
         return False

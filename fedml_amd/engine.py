@@ -1246,6 +1246,109 @@ class AggEngine:
         N.check(rc, "fa_sign_vote_sum_tiled")
         return out, flipped
 
+    MAX_DOT_K = 128  # kMaxDotK (fedml_amd/csrc/pairdot.hip): clients per fa_pairwise_dot launch
+
+    def _check_hists(self, what: str, hists, k: int, dt, numels: Sequence[int], in_ranges) -> List[int]:
+        """The histories of ``pairwise_dot``: hists[s][i] contiguous, the inputs' dtype, segment s's
+        element count, on the device, none aliasing an input, a center or another history
+        (``in_ranges``: the (first, last) byte addresses of the tensors that are read).  Returns the
+        pointers in table order."""
+        if len(hists) != len(numels):
+            raise ValueError(f"{what}: need one list of histories per segment")
+        ptrs, seen = [], list(in_ranges)
+        for s, (hs, n) in enumerate(zip(hists, numels)):
+            if len(hs) != k:
+                raise ValueError(f"{what}: segment {s}: {len(hs)} histories, expected {k} (one per client)")
+            for i, h in enumerate(hs):
+                if h.dtype != dt or h.numel() != n or not h.is_contiguous():
+                    raise ValueError(f"{what}: segment {s} client {i}: the history must be a contiguous {dt} "
+                                     f"tensor of {n} elements")
+                _require_device(h, self.device, f"segment {s} client {i} history")
+                ptrs.append(h.data_ptr())
+                if n:
+                    lo, hi = h.data_ptr(), h.data_ptr() + n * h.element_size()
+                    if any(lo < b and a < hi for a, b in seen):
+                        raise ValueError(f"{what}: segment {s} client {i}: the history aliases an input, a center "
+                                         "or another history")
+                    seen.append((lo, hi))
+        return ptrs
+
+    def pairwise_dot(self, segments: Sequence[Sequence[torch.Tensor]],
+                     centers: Optional[Sequence[torch.Tensor]] = None,
+                     hists: Optional[Sequence[Sequence[torch.Tensor]]] = None, stream=None) -> torch.Tensor:
+        """FoolsGold's pass (fa_pairwise_dot): u_i = x_i - center rounded in the dtype (``centers`` None:
+        u_i = x_i); with ``hists`` every history is updated in place, h_i = h_i + u_i rounded in the
+        dtype (bit-exact), and y_i is the stored h_i, otherwise y_i = u_i; returns G, the K x K float64
+        device matrix of the inner products sum_e y_i y_j over all segments, the diagonal included
+        (include/fedagg_robust.h: the bound on G).  segments[s][i] = client i's tensor of segment s (one
+        dtype: float32, bfloat16, float16, float64); centers[s]: segment s's center; hists[s][i]: client
+        i's history of segment s, contiguous, aliasing nothing that is read.  1 <= K <= 128: a split
+        launch would update a history more than once.  One launch."""
+        what = "pairwise_dot"
+        k = len(segments[0]) if segments else 0
+        if k == 0:
+            raise ValueError(f"{what}: no client tensors")
+        if k > self.MAX_DOT_K:
+            raise ValueError(f"{what}: at most {self.MAX_DOT_K} clients per call (got {k})")
+        if centers is not None:
+            if len(centers) != len(segments):
+                raise ValueError(f"{what}: need one center per segment")
+            if segments and len(segments[0]):
+                for s, (seg, c) in enumerate(zip(segments, centers)):
+                    self._check_center(what, c, segments[0][0].dtype, seg[0].numel() if len(seg) else 0,
+                                       f"segment {s} center")
+        # no output tensors here: client 0's (checked) inputs stand in for them, and are not written
+        dt, k, in_ptrs, numels, _ = self._flat_segments(what, segments, [seg[0] for seg in segments])
+        h_ptrs = None
+        if hists is not None:
+            read = [t for seg in segments for t in seg] + list(centers or [])
+            h_ptrs = self._check_hists(what, hists, k, dt, numels,
+                                       [(t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()) for t in read])
+        nm = N.i64_array(numels)
+        with self.lock:
+            need = int(self._lib.fa_pairwise_dot_scratch_bytes(len(segments), nm, k))
+            scratch = self._scratch("pairdot", need, stream)
+            g = torch.empty((k, k), dtype=torch.float64, device=self.device)
+            rc = self._lib.fa_pairwise_dot(self._ctx, DTYPE_CODE[dt], len(segments), nm, k, N.ptr_array(in_ptrs),
+                                           None if centers is None else N.ptr_array([t.data_ptr() for t in centers]),
+                                           None if h_ptrs is None else N.ptr_array(h_ptrs), g.data_ptr(),
+                                           scratch.data_ptr(), need, self._stream(stream))
+        N.check(rc, "fa_pairwise_dot")
+        return g
+
+    def pairwise_dot_tiled(self, buf: torch.Tensor, rows: Sequence[int], center: Optional[torch.Tensor] = None,
+                           hists: Optional[Sequence[torch.Tensor]] = None, n: Optional[int] = None,
+                           stream=None) -> torch.Tensor:
+        """``pairwise_dot`` over rows of a TILE-INTERLEAVED arena group ``buf`` [tiles, capacity, E]
+        (fa_pairwise_dot_tiled): the histories bit for bit as over the logical rows, G within the same
+        bound.  ``center`` (or None) and hists[i] (row rows[i]'s history; or None) are flat, ``n``
+        elements (default: all).  n == 0 still makes the native call: it zeroes G."""
+        what = "pairwise_dot_tiled"
+        self._check_column_dtype(what, buf.dtype)
+        if len(rows) > self.MAX_DOT_K:
+            raise ValueError(f"{what}: at most {self.MAX_DOT_K} clients per call (got {len(rows)})")
+        n, ptrs, stride = self._tiled_args(buf, rows, 0, n, what)
+        k = len(rows)
+        if center is not None:
+            self._check_center(what, center, buf.dtype, n, "center")
+        h_ptrs = None
+        if hists is not None:
+            read = [(buf.data_ptr(), buf.data_ptr() + buf.numel() * buf.element_size())]
+            if center is not None:
+                read.append((center.data_ptr(), center.data_ptr() + n * center.element_size()))
+            h_ptrs = self._check_hists(what, [list(hists)], k, buf.dtype, [n], read)
+        nm = N.i64_array([n])
+        with self.lock:
+            need = int(self._lib.fa_pairwise_dot_scratch_bytes(1, nm, k))
+            scratch = self._scratch("pairdot", need, stream)
+            g = torch.empty((k, k), dtype=torch.float64, device=self.device)
+            rc = self._lib.fa_pairwise_dot_tiled(self._ctx, DTYPE_CODE[buf.dtype], 1, nm, k, ptrs, stride,
+                                                 None if center is None else N.ptr_array([center.data_ptr()]),
+                                                 None if h_ptrs is None else N.ptr_array(h_ptrs), g.data_ptr(),
+                                                 scratch.data_ptr(), need, self._stream(stream))
+        N.check(rc, "fa_pairwise_dot_tiled")
+        return g
+
     MAX_PAIR_K = 128  # kMaxPairK (fedml_amd/csrc/robust.hip): clients per fa_pairwise_sqdist launch
 
     def pairwise_sqdist(self, segments: Sequence[Sequence[torch.Tensor]], stream=None,

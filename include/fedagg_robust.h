@@ -20,6 +20,10 @@
  *                       robust_learning_rate): the robust learning rate of Ozdayi, Kantarcioglu, Gel 2021,
  *                       the weighted sum fused with a per-coordinate vote of the clients' signs that
  *                       negates the sum where too few agree
+ *   fa_pairwise_dot, fa_pairwise_dot_tiled  core/security/defense/foolsgold_defense.py (the running sum of
+ *                       every client's updates and the pairwise cosine similarity of those sums): the
+ *                       update added into its history in place, fused with the Gram matrix of the
+ *                       stored histories; served as "fools_gold", defined by the contract below
  *   fa_pairwise_sqdist  core/security/defense/krum_defense.py:52-66 (_compute_krum_score's
  *                       compute_euclidean_distance(v_i, v_j) ** 2 for every pair)
  *   fa_pairwise_sqdist_rt  the same for bfloat16 / float16 models (differences in the model dtype)
@@ -245,6 +249,59 @@ int fa_sign_vote_sum_tiled(fa_ctx *ctx, int dtype, int32_t num_segments, const i
                            const void *const *d_in, int64_t tile_stride, const void *const *d_center,
                            const double *coef, int32_t threshold, void *const *d_out, void *d_flipped,
                            void *hip_stream);
+
+/*
+ * FoolsGold's device work (Fung, Yoon, Beschastnikh 2018, "Mitigating Sybils in Federated Learning
+ * Poisoning"): every client's update is added into its running history, in place, and the Gram matrix
+ * of the stored histories is formed in the same read.  d_in[s * k + i]: client i's tensor of segment s.
+ * d_center: NULL, or d_center[s] the center of segment s, a flat contiguous tensor of seg_numel[s]
+ * elements of `dtype` (flat in the tiled entry too).  d_hist: NULL, or d_hist[s * k + i] client i's
+ * history of segment s, flat and contiguous, of the same dtype (flat in the tiled entry too), updated in
+ * place.  d_gram: k x k float64 on the device.  d_scratch: a device buffer of at least
+ * fa_pairwise_dot_scratch_bytes(...) bytes (per-workgroup partial sums; caller-owned, reusable; one
+ * size serves every dtype).  Dtypes (F32, BF16, F16, F64; I64: FA_ERR_DTYPE), segment rules, host
+ * tables staged by the library, asynchrony on the caller's stream, the tiled addressing:
+ * fa_sign_vote_sum's.  1 <= k <= 128 (else FA_ERR_INVALID).
+ *
+ * Contract (tests/test_gpu_pairwise_dot.py).  A = float32 for F32, BF16, F16, float64 for F64; rnd
+ * rounds once to the storage type; nothing is fused in the bit-exact part.  For every element e of
+ * every segment:
+ *   u_i = x_i[e] without a center, otherwise u_i = rnd(x_i[e] - center[e])
+ *   with a history: h_i[e] = rnd(h_i[e] + u_i), stored -- bit-exact, NaNs included (each element is read
+ *     and then written by the one lane that owns it; a NaN that the rounding to BF16 / F16 produces is
+ *     the device's quiet NaN (0x7fc0 for BF16), where a host conversion may write another payload)
+ *     -- and y_i = the STORED h_i[e]
+ *   without a history: y_i = u_i, and nothing but d_gram is written
+ *   G[i][j] = sum_e y_i y_j over all segments, for all i, j: the diagonal and both triangles are
+ *     written, G[i][j] and G[j][i] with the same bit pattern
+ * Arithmetic of G: products and runs of at most 64 coordinates in float32 from exactly widened values
+ * (one fused multiply-add per product inside a run), float64 sums across runs (float64 throughout for
+ * F64) -- the scheme of fa_pairwise_sqdist.  The order is the implementation's and is fixed: no
+ * floating-point atomics, the same call gives the same k^2 bit patterns every time.
+ * Bound: with all y finite and no product below float32's normal range,
+ *   |G[i][j] - exact| <= 65 * 2^-24 * sum_e |y_i y_j| <= 3.9e-6 * sqrt(exact_ii * exact_jj)
+ * (one rounding per product plus at most 64 per run, then Cauchy-Schwarz), stated as
+ * 4e-6 * sqrt(exact_ii * exact_jj): on the diagonal a relative bound.  F64: 1e-12 on the same scale.
+ * A client whose y is all zeros gives an exactly-zero row and column.  G[i][i] is non-finite exactly
+ * when y_i holds a NaN or +-Inf, or when a float32 product or run overflows; a non-finite client taints
+ * only its own row and column.  All segments empty: d_gram is zeroed.  d_hist must not overlap d_in,
+ * d_center or itself across clients.
+ *
+ * Checked before any HIP call, in this order: ctx; (tiled) tile_stride > 0; k, num_segments, seg_numel,
+ * d_in; d_gram; dtype (I64: FA_ERR_DTYPE); (tiled) tile_stride a multiple of FA_TILE_BYTES; per
+ * non-empty segment its center (when d_center is given), history (when d_hist is given) and input
+ * pointers; the scratch.
+ */
+int fa_pairwise_dot(fa_ctx *ctx, int dtype, int32_t num_segments, const int64_t *seg_numel, int32_t k,
+                    const void *const *d_in, const void *const *d_center, void *const *d_hist,
+                    void *d_gram, void *d_scratch, size_t scratch_bytes, void *hip_stream);
+/* The same over tile-interleaved client rows (addressing and tile rules of fa_coord_median_tiled): the
+ * histories bit for bit fa_pairwise_dot's over the logical rows, G within the same bound. */
+int fa_pairwise_dot_tiled(fa_ctx *ctx, int dtype, int32_t num_segments, const int64_t *seg_numel, int32_t k,
+                          const void *const *d_in, int64_t tile_stride, const void *const *d_center,
+                          void *const *d_hist, void *d_gram, void *d_scratch, size_t scratch_bytes,
+                          void *hip_stream);
+size_t fa_pairwise_dot_scratch_bytes(int32_t num_segments, const int64_t *seg_numel, int32_t k);
 
 /*
  * Pairwise squared Euclidean distances of k float32 client vectors (2 <= k <= 128), each given
