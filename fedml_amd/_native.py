@@ -52,6 +52,10 @@ EXPORTED_SYMBOLS = (
     "fa_comm_last_op", "fa_group_plan_ex", "fa_group_ops_ex", "fa_comm_op_counts",
 )
 
+# include/fedagg_quant.h (the block-quantized int8 entries; checked by lib() like EXPORTED_SYMBOLS)
+QUANT_SYMBOLS = ("fa_quantize_q8", "fa_weighted_sum_q8")
+Q8_BLOCK_MIN, Q8_BLOCK_MAX = 16, 1024  # FA_Q8_BLOCK_MIN / FA_Q8_BLOCK_MAX
+
 # enum fa_exchange / fa_local_kind (include/fedagg_comm.h)
 XCHG_ORDERED, XCHG_ORDERED_ALL, XCHG_REDUCE, XCHG_ALL_REDUCE, XCHG_REDUCE_SCATTER = 0, 1, 2, 3, 4
 XCHG_LOOPBACK = 0x100                    # OR'ed into an ordered exchange
@@ -283,6 +287,11 @@ def _declare(L):
     L.fa_comm_local_time.argtypes = [_vp, ctypes.c_int, _P_d, _P_i64]
     L.fa_comm_last_op.restype = ctypes.c_int
     L.fa_comm_last_op.argtypes = [_vp, ctypes.c_char_p, ctypes.c_int64]
+    L.fa_quantize_q8.restype = ctypes.c_int
+    L.fa_quantize_q8.argtypes = [_vp, ctypes.c_int, ctypes.c_int32, _P_i64, ctypes.c_int32, _P_vp, _P_vp, _P_vp, _vp]
+    L.fa_weighted_sum_q8.restype = ctypes.c_int
+    L.fa_weighted_sum_q8.argtypes = [_vp, ctypes.c_int, ctypes.c_int32, _P_i64, ctypes.c_int32, ctypes.c_int32,
+                                     _P_vp, _P_vp, _P_d, _P_vp, _vp]
     L.fa_strerror.restype = ctypes.c_char_p
     L.fa_strerror.argtypes = [ctypes.c_int]
     L.fa_last_error.restype = ctypes.c_char_p
@@ -305,7 +314,7 @@ def lib():
             L = ctypes.CDLL(LIB_PATH)
         except OSError as e:
             raise FedAggNativeError(f"cannot load {LIB_PATH}: {e}") from e
-        missing = [s for s in EXPORTED_SYMBOLS if not hasattr(L, s)]
+        missing = [s for s in EXPORTED_SYMBOLS + QUANT_SYMBOLS if not hasattr(L, s)]
         if missing:
             raise FedAggNativeError(f"{LIB_PATH} lacks symbols {missing}")
         _declare(L)

@@ -891,6 +891,109 @@ class AggEngine:
         N.check(rc, "fa_finite_quantize")
         return outs
 
+    # ------------------------------------------------------------------ block-quantized int8 (q8)
+    @staticmethod
+    def _check_q8_block(what: str, block) -> int:
+        b = int(block)
+        if b != block or b < N.Q8_BLOCK_MIN or b > N.Q8_BLOCK_MAX or b & (b - 1):
+            raise ValueError(f"{what}: block {block!r} must be a power of two in "
+                             f"[{N.Q8_BLOCK_MIN}, {N.Q8_BLOCK_MAX}]")
+        return b
+
+    def quantize_q8(self, xs: Sequence[torch.Tensor], block: int = 128,
+                    outs: Optional[Tuple[Sequence[torch.Tensor], Sequence[torch.Tensor]]] = None,
+                    stream=None) -> Tuple[List[torch.Tensor], List[torch.Tensor]]:
+        """Block-quantize same-dtype device tensors (float32, bfloat16 or float16) to the q8 format of
+        include/fedagg_quant.h in one launch (fa_quantize_q8).  Returns (qs, scales): qs[s] is int8 with
+        xs[s]'s shape, scales[s] is float32 with ceil(numel / block) elements.  ``outs``: (qs, scales) to
+        write into."""
+        block = self._check_q8_block("quantize_q8", block)
+        if len(xs) == 0:
+            return [], []
+        dt = xs[0].dtype
+        if dt not in (torch.float32, torch.bfloat16, torch.float16):
+            raise TypeError(f"quantize_q8: unsupported dtype {dt} (float32, bfloat16, float16)")
+        qs, scales = [], []
+        for s, t in enumerate(xs):
+            if t.dtype != dt:
+                raise TypeError(f"quantize_q8: tensor {s} is {t.dtype}, expected {dt}")
+            _require_device(t, self.device, f"tensor {s}")
+            nb = -(-t.numel() // block)
+            if outs is not None:
+                q, sc = outs[0][s], outs[1][s]
+                if q.dtype != torch.int8 or q.numel() != t.numel():
+                    raise ValueError(f"quantize_q8: q output {s} must be int8 with {t.numel()} elements")
+                if sc.dtype != torch.float32 or sc.numel() != nb:
+                    raise ValueError(f"quantize_q8: scale output {s} must be float32 with {nb} elements")
+                _require_device(q, self.device, f"q output {s}")
+                _require_device(sc, self.device, f"scale output {s}")
+            else:
+                q = torch.empty(t.shape, dtype=torch.int8, device=self.device)
+                sc = torch.empty(nb, dtype=torch.float32, device=self.device)
+            qs.append(q)
+            scales.append(sc)
+        rc = self._lib.fa_quantize_q8(
+            self._ctx, DTYPE_CODE[dt], len(xs), N.i64_array([t.numel() for t in xs]), block,
+            N.ptr_array([t.data_ptr() for t in xs]), N.ptr_array([q.data_ptr() for q in qs]),
+            N.ptr_array([sc.data_ptr() for sc in scales]), self._stream(stream))
+        N.check(rc, "fa_quantize_q8")
+        return qs, scales
+
+    def weighted_sum_q8(self, q_segments: Sequence[Sequence[torch.Tensor]],
+                        scale_segments: Sequence[Sequence[torch.Tensor]], mode: int,
+                        coef: Optional[Sequence[float]] = None, block: int = 128,
+                        outs: Optional[Sequence[torch.Tensor]] = None, stream=None) -> List[torch.Tensor]:
+        """Fused dequantize-and-sum of q8 client tensors (fa_weighted_sum_q8), one launch:
+        q_segments[s][i] / scale_segments[s][i] = client i's int8 data and float32 scales for key s, as
+        ``weighted_sum_multi`` takes its segments.  ``mode`` is MUL_W (``coef`` = the weights) or SUM.
+        Returns one float32 tensor per key with the q tensors' shape.  k = 1 with SUM dequantizes."""
+        block = self._check_q8_block("weighted_sum_q8", block)
+        if len(q_segments) != len(scale_segments):
+            raise ValueError("weighted_sum_q8: q_segments and scale_segments differ in length")
+        if len(q_segments) == 0:
+            return []
+        k = len(q_segments[0])
+        if k == 0:
+            raise ValueError("weighted_sum_q8: no client tensors")
+        if mode not in (MUL_W, SUM):
+            raise ValueError(f"weighted_sum_q8: mode {mode} not supported (MUL_W, SUM)")
+        if mode != SUM and (coef is None or len(coef) != k):
+            raise ValueError("weighted_sum_q8: need one coefficient per client")
+        numels, q_ptrs, s_ptrs, results = [], [], [], []
+        for s, (qseg, sseg) in enumerate(zip(q_segments, scale_segments)):
+            if len(qseg) != k or len(sseg) != k:
+                raise ValueError(f"segment {s}: {len(qseg)} q and {len(sseg)} scale tensors, expected {k}")
+            shape, n = qseg[0].shape, qseg[0].numel()
+            nb = -(-n // block)
+            for i, (q, sc) in enumerate(zip(qseg, sseg)):
+                if q.dtype != torch.int8 or sc.dtype != torch.float32:
+                    raise TypeError(f"segment {s} client {i}: q must be int8 and scale float32 "
+                                    f"(got {q.dtype}, {sc.dtype})")
+                if q.shape != shape:
+                    raise ValueError(f"segment {s} client {i}: shape {tuple(q.shape)} != {tuple(shape)}")
+                if sc.numel() != nb:
+                    raise ValueError(f"segment {s} client {i}: {sc.numel()} scales, expected {nb} "
+                                     f"for {n} elements in blocks of {block}")
+                _require_device(q, self.device, f"segment {s} client {i} q")
+                _require_device(sc, self.device, f"segment {s} client {i} scale")
+                q_ptrs.append(q.data_ptr())
+                s_ptrs.append(sc.data_ptr())
+            if outs is not None:
+                o = outs[s]
+                if o.dtype != torch.float32 or o.numel() != n:
+                    raise ValueError(f"segment {s}: output must be float32 with {n} elements")
+                _require_device(o, self.device, f"segment {s} output")
+            else:
+                o = torch.empty(shape, dtype=torch.float32, device=self.device)
+            results.append(o)
+            numels.append(n)
+        rc = self._lib.fa_weighted_sum_q8(
+            self._ctx, int(mode), len(q_segments), N.i64_array(numels), k, block, N.ptr_array(q_ptrs),
+            N.ptr_array(s_ptrs), N.f64_array(coef) if mode != SUM else None,
+            N.ptr_array([o.data_ptr() for o in results]), self._stream(stream))
+        N.check(rc, "fa_weighted_sum_q8")
+        return results
+
     def lcc_decode(self, coef: Sequence[Sequence[int]], f: torch.Tensor, prime: int, n_out: int,
                    stream=None) -> torch.Tensor:
         """First n_out entries of np.mod(coef.dot(f), p) (int64 wrap), f an int64 (k x m) device tensor."""

@@ -20,6 +20,7 @@ import logging
 from collections import OrderedDict
 from typing import List, Tuple
 
+from .quantized import Q8Tensor, aggregate_q8
 from .state_dict_agg import MUL_W, SUM, aggregate
 
 # args.ml_engine values (python/fedml/core/common/ml_engine_backend.py)
@@ -40,9 +41,31 @@ class FedMLAggOperator:
         return model_aggregator(args, raw_grad_list, training_num)
 
 
+def _holds_q8(raw_grad_list) -> bool:
+    """Client 0's dicts hold a block-quantized tensor (quantized.Q8Tensor): the round is a q8 round.
+    aggregate_q8 then requires every client to agree key by key."""
+    if not raw_grad_list:
+        return False
+    return any(isinstance(v, Q8Tensor) for d in raw_grad_list[0][1:] if isinstance(d, dict) for v in d.values())
+
+
+def _q8_aggregator(args, raw_grad_list, training_num):
+    """Block-quantized uploads (not in the reference): the FedAvg / FedProx weighted sum and the
+    FedAvg_seq / FedDyn plain sum on the fused dequantize-and-sum kernel."""
+    opt = args.federated_optimizer
+    if opt in ("FedAvg", "FedProx"):
+        return aggregate_q8([p for _, p in raw_grad_list], MUL_W, [n / training_num for n, _ in raw_grad_list])
+    if opt in ("FedAvg_seq", "FedDyn"):
+        return aggregate_q8([p for _, p in raw_grad_list], SUM)
+    raise NotImplementedError(f"federated_optimizer={opt!r}: block-quantized (Q8Tensor) state_dicts are aggregated "
+                              "for FedAvg, FedProx, FedAvg_seq and FedDyn only")
+
+
 def torch_aggregator(args, raw_grad_list, training_num):
     """Reference: agg_operator.py:33-134, one branch per federated optimizer."""
     opt = args.federated_optimizer
+    if _holds_q8(raw_grad_list):
+        return _q8_aggregator(args, raw_grad_list, training_num)
     if opt in ("FedAvg", "FedProx"):
         counts = [n for n, _ in raw_grad_list]
         return aggregate([p for _, p in raw_grad_list], MUL_W, [n / training_num for n in counts])
