@@ -303,20 +303,36 @@ def test_fedopt_fused_server_step_golden(name, where):
                 assert_dict_bits(OrderedDict([(k, got[k])]), OrderedDict([(k, exp[k])]), f"{name} round {r}")
 
 
+def _fma32(a, b, c):
+    """float32 fma(a, b, c) of float32 tensors, exactly: the product of two float32 is exact in float64,
+    the sum is rounded to odd there (the other neighbour whenever the float64 sum is inexact and even),
+    and rounding a round-to-odd float64 to float32 is the one rounding of the exact value.  A plain
+    float64 sum rounds twice: it loses an addend below its last bit that breaks a float32 tie."""
+    s, c = a.double() * b.double(), c.double()
+    t = s + c
+    v = t - s
+    err = (s - (t - v)) + (c - v)  # the exact error of the sum (TwoSum)
+    bits = t.view(torch.int64)
+    fix = torch.isfinite(t) & (err != 0) & ((bits & 1) == 0)
+    away = (err > 0) == (t > 0)
+    one = torch.ones_like(bits)
+    return torch.where(fix, bits + torch.where(away, one, -one), bits).view(torch.float64).float()
+
+
 def _rmsprop_cr(p, avg, sq, buf, lr, alpha, eps, wd, momentum):
     """torch.optim.RMSprop's CPU op sequence (rmsprop.py _single_tensor_rmsprop, ATen's contracted
     addcmul / addcdiv) with a CORRECTLY ROUNDED sqrt, float32 via exact float64 emulation."""
     f, d = (lambda x: x.float()), (lambda x: x.double())
     g = p - avg
     if wd:
-        g = f(d(p) * wd32(wd) + d(g))
+        g = _fma32(p, torch.tensor(wd, dtype=torch.float32), g)
     s1 = torch.tensor(1 - alpha, dtype=torch.float32)
-    sq = f(d(s1 * g) * d(g) + d(sq * torch.tensor(alpha, dtype=torch.float32)))
+    sq = _fma32(s1 * g, g, sq * torch.tensor(alpha, dtype=torch.float32))
     den = f(d(sq).sqrt()) + torch.tensor(eps, dtype=torch.float32)
     nlr = torch.tensor(-lr, dtype=torch.float32)
     if momentum:
         buf = buf * torch.tensor(momentum, dtype=torch.float32) + g / den
-        p = f(d(buf) * d(nlr) + d(p))
+        p = _fma32(buf, nlr, p)
     else:
         p = p + (nlr * g) / den
     return p, sq, buf
