@@ -308,6 +308,27 @@ size_t fa_pairwise_dot_scratch_bytes(int32_t num_segments, const int64_t *seg_nu
  * as num_segments pieces (d_in[s * k + i], seg_numel[s] elements): d_dist = k x k float64 device
  * matrix (symmetric, zero diagonal).  d_scratch: device buffer of at least
  * fa_pairwise_sqdist_scratch_bytes(...) bytes (per-block partial sums; caller-owned, reusable).
+ *
+ * Contract of fa_pairwise_sqdist and fa_pairwise_sqdist_rt (tests/test_gpu_krum_exact.py, on inputs of
+ * four or five chunks per workgroup, one segment and many, 16-byte aligned and not).  For every pair,
+ *   D[i][j] = sum_e rnd(x_i[e] - x_j[e])^2 over all segments,
+ * rnd the rounding to diff_dtype (none for F32).  Arithmetic: the difference, its rounding and the
+ * square in float32, float32 sums over runs of at most 64 coordinates (one fused multiply-add per
+ * coordinate inside a run), float64 sums across runs; float64 throughout for F64.  The order is the
+ * implementation's and is fixed: no floating-point atomics, the same call gives the same k^2 bit
+ * patterns every time; D[i][j] and D[j][i] carry the same bits and the diagonal is +0.0.
+ * Exactness: where every difference (after rnd), every square and every run sum is representable in
+ * float32 and the total in float64, D is the exact value, bit for bit -- e.g. integer inputs of
+ * magnitude <= 15 at any length below 2^53 / 900, or the same times a power of two while the squares
+ * stay inside float32's normal range.  Otherwise relative error <= 1e-6 against the exact sum.
+ * Non-finite inputs: a client that holds a NaN or +-Inf taints only its own row and column; every
+ * entry between two finite clients has the bits the same call gives with that value replaced by 0
+ * (no other client's sums read it).  The tainted entries have
+ * the class float64 arithmetic gives: an Inf against a finite value +Inf, an Inf against an equal Inf
+ * at the same coordinate (Inf - Inf), and anything against a NaN, NaN.  The Gram form's guard hands
+ * such inputs to these kernels (kappa_max = +inf).
+ * Range: a square below float32's normal range may be lost (flushed or rounded as a subnormal), and a
+ * float32 square or run sum that overflows gives +Inf in that entry -- stated, not tested.
  */
 int fa_pairwise_sqdist(fa_ctx *ctx, int32_t num_segments, const int64_t *seg_numel, int32_t k,
                        const void *const *d_in, void *d_dist, void *d_scratch, size_t scratch_bytes,
