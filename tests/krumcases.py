@@ -138,17 +138,19 @@ def boundary_positions(sizes, chunk: int, cap: int, count: int) -> list:
     return out[:count]
 
 
-def place(table: torch.Tensor, sizes, aligned: bool, dtype=torch.float32) -> tuple:
+def place(table: torch.Tensor, sizes, aligned, dtype=torch.float32) -> tuple:
     """(buffer, segments): the [K, n] table widened to ``dtype`` on the table's device and cut into
     ``sizes``; segments[s][i] is client i's piece s, a view that starts on a 16-byte boundary
-    (aligned) or one element past one.  The gaps between the pieces hold NaN: a read outside a piece
-    poisons the result."""
+    (aligned) or one element past one -- ``aligned`` is one flag for every piece or one per piece.
+    The gaps between the pieces hold NaN: a read outside a piece poisons the result."""
     K, n = table.shape
     assert sum(sizes) == n
     per16 = 16 // torch.empty(0, dtype=dtype).element_size()
+    flags = [aligned] * len(sizes) if isinstance(aligned, bool) else list(aligned)
+    assert len(flags) == len(sizes)
     offs, cur = [], 0
-    for s in sizes:
-        cur = -(-cur // per16) * per16 + (0 if aligned else 1)
+    for s, al in zip(sizes, flags):
+        cur = -(-cur // per16) * per16 + (0 if al else 1)
         offs.append(cur)
         cur += s
     width = -(-(cur + 1) // per16) * per16

@@ -294,6 +294,19 @@ def test_wide_votes(eng, k):
         assert torch.equal(torch.sign(got[0]), torch.where(odd, -sign, sign))  # sum coef = 1, every |x| >= 0.1
 
 
+def test_count_over_more_than_1024_workgroups(eng):
+    """k_sign_vote_count is one workgroup of 1,024 lanes striding over the workgroups' counts; every
+    other case here has at most twenty of them.  n = 2049 * 1024 + 5 float32 elements are 2,050
+    workgroups, so each lane takes three strides: the count equals the restatement's exactly and out
+    matches bit for bit."""
+    k, n = 3, 2049 * 1024 + 5
+    assert -(-n // slot_elems(torch.float32)) > 2 * 1024
+    g = torch.Generator().manual_seed(2450)
+    x, c = voting_pair(g, k, n, torch.float32)
+    got = run_flat(eng, x, c, [n], 0, coefs(g, k), [third(k)], f"count k={k} n={n}", band=third(k))
+    assert 0 < got[third(k)][1] < n
+
+
 # ----------------------------------------------------------------------------- in place, tiled, determinism
 @pytest.mark.parametrize("dt,k", [(torch.float32, 8), (torch.float32, 40), (torch.bfloat16, 3)], ids=str)
 def test_in_place_equals_separate_buffers(eng, dt, k):
