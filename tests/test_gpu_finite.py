@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from golden_io import FINITE_PREFIXES, client_dicts, expected_dicts, list_cases, load_case
+from lcccases import adversarial as _adversarial
 from refcases import MOD_EACH, MOD_END, MOD_FIRST, REAL_F64, assert_dict_bits, bits_equal, sa_order_and_flags
 
 pytestmark = pytest.mark.gpu
@@ -265,18 +266,6 @@ def test_mt_randint_sum_edges(eng):
 
 
 # ----------------------------------------------------------------------------- vs the C oracle
-def _adversarial(g, n, p):
-    v = torch.randint(0, p, (n,), generator=g, dtype=torch.int64)
-    sel = torch.randint(0, 8, (n,), generator=g)
-    big = torch.randint(-2 ** 62, 2 ** 62, (n,), generator=g, dtype=torch.int64) * 2
-    v = torch.where(sel == 1, -v, v)
-    v = torch.where(sel == 2, big, v)
-    v = torch.where(sel == 3, torch.full_like(v, 2 ** 63 - 1), v)
-    v = torch.where(sel == 4, torch.full_like(v, -2 ** 63), v)
-    v = torch.where(sel == 5, v + p, v)
-    return v
-
-
 @pytest.mark.parametrize("p", [2 ** 15 - 19, 2 ** 31 - 1, 2 ** 61 - 1, 2 ** 62 + 135, 2 ** 63 - 25, 7])
 @pytest.mark.parametrize("flags", [0, MOD_EACH, MOD_END, MOD_EACH | MOD_END, MOD_FIRST | MOD_EACH | MOD_END])
 @pytest.mark.parametrize("adversarial", [False, True])
