@@ -54,6 +54,10 @@ EXPORTED_SYMBOLS = (
 
 # include/fedagg_quant.h (the block-quantized int8 entries; checked by lib() like EXPORTED_SYMBOLS)
 QUANT_SYMBOLS = ("fa_quantize_q8", "fa_weighted_sum_q8")
+# include/fedagg_dp.h (the differential-privacy entries; checked by lib() like EXPORTED_SYMBOLS)
+DP_SYMBOLS = ("fa_noise_words", "fa_add_noise", "fa_centered_sum_noise", "fa_centered_sum_noise_tiled")
+NOISE_GAUSSIAN, NOISE_LAPLACE = 0, 1  # enum fa_noise_mech
+NOISE_Z_ABS_ERR = 2.4e-6              # FA_NOISE_Z_ABS_ERR
 Q8_BLOCK_MIN, Q8_BLOCK_MAX = 16, 1024  # FA_Q8_BLOCK_MIN / FA_Q8_BLOCK_MAX
 
 # enum fa_exchange / fa_local_kind (include/fedagg_comm.h)
@@ -88,6 +92,7 @@ _P_vp = ctypes.POINTER(ctypes.c_void_p)
 _P_d = ctypes.POINTER(ctypes.c_double)
 _P_i64 = ctypes.POINTER(ctypes.c_int64)
 _P_i32 = ctypes.POINTER(ctypes.c_int32)
+_P_u32 = ctypes.POINTER(ctypes.c_uint32)
 
 
 def _declare(L):
@@ -292,6 +297,18 @@ def _declare(L):
     L.fa_weighted_sum_q8.restype = ctypes.c_int
     L.fa_weighted_sum_q8.argtypes = [_vp, ctypes.c_int, ctypes.c_int32, _P_i64, ctypes.c_int32, ctypes.c_int32,
                                      _P_vp, _P_vp, _P_d, _P_vp, _vp]
+    L.fa_noise_words.restype = ctypes.c_int
+    L.fa_noise_words.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64,
+                                 ctypes.c_int64, _vp, _vp]
+    L.fa_add_noise.restype = ctypes.c_int
+    L.fa_add_noise.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32,
+                               ctypes.c_int32, _P_i64, _P_u32, _P_vp, _P_vp, _vp]
+    _noise_tail = [_P_vp, _P_d, ctypes.c_int, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _P_u32, _P_vp, _vp]
+    L.fa_centered_sum_noise.restype = ctypes.c_int
+    L.fa_centered_sum_noise.argtypes = [_vp, ctypes.c_int, ctypes.c_int32, _P_i64, ctypes.c_int32, _P_vp] + _noise_tail
+    L.fa_centered_sum_noise_tiled.restype = ctypes.c_int
+    L.fa_centered_sum_noise_tiled.argtypes = [_vp, ctypes.c_int, ctypes.c_int32, _P_i64, ctypes.c_int32, _P_vp,
+                                              ctypes.c_int64] + _noise_tail
     L.fa_strerror.restype = ctypes.c_char_p
     L.fa_strerror.argtypes = [ctypes.c_int]
     L.fa_last_error.restype = ctypes.c_char_p
@@ -314,7 +331,7 @@ def lib():
             L = ctypes.CDLL(LIB_PATH)
         except OSError as e:
             raise FedAggNativeError(f"cannot load {LIB_PATH}: {e}") from e
-        missing = [s for s in EXPORTED_SYMBOLS + QUANT_SYMBOLS if not hasattr(L, s)]
+        missing = [s for s in EXPORTED_SYMBOLS + QUANT_SYMBOLS + DP_SYMBOLS if not hasattr(L, s)]
         if missing:
             raise FedAggNativeError(f"{LIB_PATH} lacks symbols {missing}")
         _declare(L)
@@ -345,3 +362,7 @@ def i64_array(vals):
 
 def i32_array(vals):
     return (ctypes.c_int32 * len(vals))(*[int(v) for v in vals])
+
+
+def u32_array(vals):
+    return (ctypes.c_uint32 * len(vals))(*[int(v) for v in vals])

@@ -664,6 +664,91 @@ class ClientArena:
             info.update(res)
         return self.layout.carve(outs)
 
+    TILED_SEG_BASE = 1 << 31  # dp_aggregate: the segment id of a tiled arena's dtype group g is this + g
+
+    def dp_aggregate(self, counts: Sequence[float], clip: float, scale: float, mech, seed: int, round: int,
+                     center: Optional[Dict[torch.dtype, torch.Tensor]] = None,
+                     clients: Optional[Sequence[int]] = None,
+                     out: Optional[Dict[torch.dtype, torch.Tensor]] = None,
+                     info: Optional[dict] = None) -> "OrderedDict[str, torch.Tensor]":
+        """DP-FedAvg's server step (McMahan et al. 2018; include/fedagg_dp.h, fedml_amd/dp.py) over the
+        given client rows (default: all) weighted by ``counts`` (aligned with ``clients``): the norms
+        |x_i - center| over all float keys as one vector from ONE distance-only launch per dtype group
+        (added across groups on the host, as ``centered_clip`` does), the weights w_i min(1, clip /
+        |x_i - center|) with w_i = counts_i / sum(counts), and center + the clipped weighted sum of
+        the x_i - center + noise of scale ``scale`` in ONE fa_centered_sum_noise launch per dtype group.
+        ``center``: dtype -> flat device tensor of the group's elements in the layout's order (only
+        read, unless it is ``out`` itself); None: the origin (the norms are |x_i|, the sum is over the
+        rows' own values).  Client-major arenas launch over the keys' row views, the key's position in
+        the layout as its segment id -- the bits of the same keys given as separate tensors; tiled
+        arenas go through the tiled entry with ONE segment per dtype group (id TILED_SEG_BASE + the
+        group's position, the element index that of the packed group, alignment padding included).
+        Float groups only.  ``info`` (optional dict) receives ``d2`` and ``scales``.  Returns per-key
+        views."""
+        from .dp import clip_scales
+        rows = list(range(self.capacity)) if clients is None else list(clients)
+        if not rows:
+            raise ValueError("dp: no client rows")
+        if len(counts) != len(rows):
+            raise ValueError("dp: need one count per client row")
+        if any(dt not in (torch.float32, torch.bfloat16, torch.float16, torch.float64) for dt in self.bufs):
+            raise TypeError("dp: the arena holds a non-float dtype group")
+        counts = [float(c) for c in counts]
+        if not all(c > 0 and math.isfinite(c) for c in counts):
+            raise ValueError("dp: every client weight must be positive and finite")
+        if center is not None:
+            for dt in self.bufs:
+                c = center.get(dt)
+                n = self.layout.group_numel[dt]
+                if c is None or c.dtype != dt or c.numel() != n or not c.is_contiguous():
+                    raise ValueError(f"dp: center[{dt}] must be a contiguous {dt} tensor of {n} elements")
+        self._wait_ingest()
+        eng = self.engine
+        tot = sum(counts)
+        w = [c / tot for c in counts]
+        pos = {key: i for i, key in enumerate(self.layout.keys)}
+        outs: Dict[torch.dtype, torch.Tensor] = {}
+        cens: Dict[torch.dtype, torch.Tensor] = {}
+        for dt, buf in self.bufs.items():
+            n = self.layout.group_numel[dt]
+            o = out[dt] if out is not None else None
+            outs[dt] = o if o is not None else torch.empty(n, dtype=dt, device=buf.device)
+            # the norms' pass needs a center: the origin when none is given
+            cens[dt] = center[dt].reshape(-1) if center is not None else torch.zeros(n, dtype=dt, device=buf.device)
+
+        def keys_of(dt):  # (segment id, offset, elements) of the group's non-empty keys
+            return [(pos[key], off, kn) for key, (kdt, off, _, kn) in self.layout.where.items() if kdt == dt and kn]
+
+        stats = []
+        for dt, buf in self.bufs.items():
+            n = self.layout.group_numel[dt]
+            if self.tiled:
+                stats.append(eng.centered_sum_sqdist_tiled(buf, rows, cens[dt], None, n=n)[1])
+            else:
+                ks = keys_of(dt)
+                stats.append(eng.centered_sum_sqdist([[buf[r][a:a + kn] for r in rows] for _, a, kn in ks],
+                                                     [cens[dt][a:a + kn] for _, a, kn in ks], None)[1])
+        d2, _ = sum_stats(stats)
+        scales = clip_scales(w, d2, clip)
+        if info is not None:
+            info.update(d2=list(d2), scales=list(scales))
+        for g, (dt, buf) in enumerate(self.bufs.items()):
+            n, o = self.layout.group_numel[dt], outs[dt].reshape(-1)
+            c = cens[dt] if center is not None else None
+            if self.tiled:
+                eng.centered_sum_noise_tiled(buf, rows, c, scales, mech, scale, seed, round, self.TILED_SEG_BASE + g,
+                                             n=n, out=o)
+            else:
+                ks = keys_of(dt)
+                if c is None:  # the padding between keys: the center's
+                    o.zero_()
+                elif o.data_ptr() != c.data_ptr():
+                    o.copy_(c)
+                eng.centered_sum_noise([[buf[r][a:a + kn] for r in rows] for _, a, kn in ks],
+                                       None if c is None else [c[a:a + kn] for _, a, kn in ks], scales, mech, scale,
+                                       seed, round, [sid for sid, _, _ in ks], outs=[o[a:a + kn] for _, a, kn in ks])
+        return self.layout.carve(outs)
+
     def sign_vote_sum(self, counts: Sequence[float], threshold: int, server_lr: float = 1.0,
                       center: Optional[Dict[torch.dtype, torch.Tensor]] = None,
                       clients: Optional[Sequence[int]] = None,

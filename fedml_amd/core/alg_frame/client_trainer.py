@@ -2,12 +2,16 @@
 
 The trainer-side counterpart of ServerAggregator: a client produces ``(num_samples, state_dict)``
 -- the exact input format of the aggregation engine (``get_model_params`` returns a state_dict,
-cf. ml/trainer/my_model_trainer_classification.py:15-16 in the reference).  Local DP and data
-poisoning hooks (core/dp, core/security) are outside this engine and stay off.
+cf. ml/trainer/my_model_trainer_classification.py:15-16 in the reference).  Local DP
+(``dp_solution_type="ldp"``, fedml_amd/core/dp) adds the client's noise to its parameters after local
+training, on the HIP engine; the data poisoning hooks (core/security) are outside this engine and stay
+off.
 """
 from __future__ import annotations
 
 from abc import ABC, abstractmethod
+
+from ..dp.fedml_differential_privacy import FedMLDifferentialPrivacy
 
 
 class ClientTrainer(ABC):
@@ -18,9 +22,9 @@ class ClientTrainer(ABC):
         self.local_train_dataset = None
         self.local_test_dataset = None
         self.local_sample_number = 0
-        for flag in ("enable_dp", "enable_attack"):
-            if getattr(args, flag, False):
-                raise NotImplementedError(f"args.{flag}=True is outside the MI355X aggregation engine")
+        if getattr(args, "enable_attack", False):
+            raise NotImplementedError("args.enable_attack=True is outside the MI355X aggregation engine")
+        FedMLDifferentialPrivacy.get_instance().init(args)
 
     def set_id(self, trainer_id):
         self.id = trainer_id
@@ -49,7 +53,11 @@ class ClientTrainer(ABC):
         ...
 
     def on_after_local_training(self, train_data, device, args):
-        pass
+        """Reference :50-56: under local DP the client's parameters get its noise (its seed is derived
+        from ``self.id``)."""
+        dp = FedMLDifferentialPrivacy.get_instance()
+        if dp.is_local_dp_enabled():
+            self.set_model_params(dp.add_local_noise(self.get_model_params(), client_id=self.id))
 
     def test(self, test_data, device, args):
         pass

@@ -6,6 +6,7 @@ and launches on the current torch stream.  All arithmetic happens in the HIP ker
 """
 from __future__ import annotations
 
+import math
 import os
 import threading
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -1348,6 +1349,131 @@ class AggEngine:
                                               self._stream(stream))
         N.check(rc, "fa_sign_vote_sum_tiled")
         return out, flipped
+
+    # -- differential privacy (include/fedagg_dp.h; the host side: fedml_amd/dp.py) -----------------
+
+    @staticmethod
+    def _noise_args(what: str, mech, scale, seed, round, seg_ids, nseg: int):
+        """(mech code, scale, seed, round, the uint32 ids) checked as the native entries check them."""
+        from .dp import mech_code
+        m = mech_code(mech)
+        scale = float(scale)
+        if not (scale >= 0.0 and math.isfinite(scale)):
+            raise ValueError(f"{what}: scale must be finite and >= 0 (got {scale})")
+        for name, v, bits in (("seed", seed, 64), ("round", round, 32)):
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < (1 << bits):
+                raise ValueError(f"{what}: {name} must be an integer in [0, 2^{bits}) (got {v!r})")
+        if seg_ids is None or len(seg_ids) != nseg:
+            raise ValueError(f"{what}: need one segment id per segment")
+        for v in seg_ids:
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < (1 << 32):
+                raise ValueError(f"{what}: a segment id must be an integer in [0, 2^32) (got {v!r})")
+        return m, scale, seed, round, N.u32_array(seg_ids)
+
+    def noise_words(self, seed: int, round: int, seg_id: int, first_block: int, nblocks: int,
+                    stream=None) -> torch.Tensor:
+        """The generator's raw words (fa_noise_words): an [nblocks, 4] int32 device tensor holding the
+        uint32 words of blocks first_block .. first_block + nblocks - 1 of (seed, round, seg_id)."""
+        what = "noise_words"
+        _, _, seed, round, ids = self._noise_args(what, 0, 0.0, seed, round, [seg_id], 1)
+        if not (isinstance(first_block, int) and isinstance(nblocks, int)) or first_block < 0 or nblocks < 0 \
+                or first_block + nblocks > (1 << 64):
+            raise ValueError(f"{what}: need 0 <= first_block, 0 <= nblocks, first_block + nblocks <= 2^64")
+        out = torch.empty((nblocks, 4), dtype=torch.int32, device=self.device)
+        rc = self._lib.fa_noise_words(self._ctx, seed, round, ids[0], first_block, nblocks, out.data_ptr(),
+                                      self._stream(stream))
+        N.check(rc, "fa_noise_words")
+        return out
+
+    def add_noise(self, tensors: Optional[Sequence[torch.Tensor]], mech, scale: float, seed: int, round: int,
+                  seg_ids: Sequence[int], outs: Optional[Sequence[torch.Tensor]] = None,
+                  stream=None) -> List[torch.Tensor]:
+        """out[s][e] = rnd(x + t), t = rnd(scale * z) the noise of (seed, round, seg_ids[s], e)
+        (fa_add_noise, include/fedagg_dp.h): ``mech`` "gaussian" or "laplace"; ``tensors`` contiguous
+        tensors of one dtype (float32, bfloat16, float16, float64) on the engine's device; outs[s] may
+        be tensors[s] itself (in place).  ``tensors`` None: x = +0 and ``outs`` (required) receive the
+        noise itself.  scale 0 returns the inputs' bits.  One launch.  Returns the outputs."""
+        what = "add_noise"
+        src = outs if tensors is None else tensors
+        if not src:
+            raise ValueError(f"{what}: no tensors")
+        dt = src[0].dtype
+        self._check_column_dtype(what, dt)
+        for s, t in enumerate(src):
+            if t.dtype != dt or not t.is_contiguous():
+                raise ValueError(f"{what}: tensor {s} must be a contiguous {dt} tensor")
+            _require_device(t, self.device, f"tensor {s}")
+        if tensors is None:
+            results = list(outs)
+        elif outs is None:
+            results = [torch.empty_like(t) for t in tensors]
+        else:
+            if len(outs) != len(tensors):
+                raise ValueError(f"{what}: need one output per tensor")
+            for s, (o, t) in enumerate(zip(outs, tensors)):
+                if o.dtype != dt or o.numel() != t.numel() or not o.is_contiguous():
+                    raise ValueError(f"{what}: output {s} must be a contiguous {dt} tensor of {t.numel()} elements")
+                _require_device(o, self.device, f"output {s}")
+            results = list(outs)
+        m, scale, seed, round, ids = self._noise_args(what, mech, scale, seed, round, seg_ids, len(src))
+        rc = self._lib.fa_add_noise(self._ctx, DTYPE_CODE[dt], m, scale, seed, round, len(src),
+                                    N.i64_array([t.numel() for t in src]), ids,
+                                    None if tensors is None else N.ptr_array([t.data_ptr() for t in tensors]),
+                                    N.ptr_array([o.data_ptr() for o in results]), self._stream(stream))
+        N.check(rc, "fa_add_noise")
+        return results
+
+    def centered_sum_noise(self, segments: Sequence[Sequence[torch.Tensor]],
+                           centers: Optional[Sequence[torch.Tensor]], coef: Sequence[float], mech, scale: float,
+                           seed: int, round: int, seg_ids: Sequence[int],
+                           outs: Optional[Sequence[torch.Tensor]] = None, stream=None) -> List[torch.Tensor]:
+        """The clipped sum and the noise in one read (fa_centered_sum_noise): y = ``sign_vote_sum``'s
+        out at threshold 0 for the same segments, centers and coefficients, out = rnd(y + t) with t
+        as in ``add_noise`` -- bit for bit ``add_noise`` of that y.  outs[s] may be centers[s] itself.
+        One launch.  Returns the outputs."""
+        what = "centered_sum_noise"
+        if centers is not None:
+            if len(centers) != len(segments):
+                raise ValueError(f"{what}: need one center per segment")
+            if segments and len(segments[0]):
+                for s, (seg, c) in enumerate(zip(segments, centers)):
+                    self._check_center(what, c, segments[0][0].dtype, seg[0].numel() if len(seg) else 0,
+                                       f"segment {s} center")
+        dt, k, in_ptrs, numels, results = self._flat_segments(what, segments, outs)
+        c = self._sqdist_coef(what, coef, k)
+        m, scale, seed, round, ids = self._noise_args(what, mech, scale, seed, round, seg_ids, len(segments))
+        rc = self._lib.fa_centered_sum_noise(self._ctx, DTYPE_CODE[dt], len(segments), N.i64_array(numels), k,
+                                             N.ptr_array(in_ptrs),
+                                             None if centers is None else N.ptr_array([t.data_ptr() for t in centers]),
+                                             c, m, scale, seed, round, ids,
+                                             N.ptr_array([o.data_ptr() for o in results]), self._stream(stream))
+        N.check(rc, "fa_centered_sum_noise")
+        return results
+
+    def centered_sum_noise_tiled(self, buf: torch.Tensor, rows: Sequence[int], center: Optional[torch.Tensor],
+                                 coef: Sequence[float], mech, scale: float, seed: int, round: int, seg_id: int,
+                                 n: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                                 stream=None) -> torch.Tensor:
+        """``centered_sum_noise`` over rows of a TILE-INTERLEAVED arena group ``buf`` [tiles, capacity,
+        E] (fa_centered_sum_noise_tiled), one segment with id ``seg_id``: the same out, bit for bit, as
+        over the logical rows.  ``center`` (or None) is flat, ``n`` elements (default: all), like
+        ``out``, which may be ``center`` itself.  Returns out."""
+        what = "centered_sum_noise_tiled"
+        self._check_column_dtype(what, buf.dtype)
+        n, ptrs, stride = self._tiled_args(buf, rows, 0, n, what)
+        k = len(rows)
+        if center is not None:
+            self._check_center(what, center, buf.dtype, n, "center")
+        c = self._sqdist_coef(what, coef, k)
+        m, scale, seed, round, ids = self._noise_args(what, mech, scale, seed, round, [seg_id], 1)
+        out = self._tiled_out(what, buf, n, out)
+        rc = self._lib.fa_centered_sum_noise_tiled(self._ctx, DTYPE_CODE[buf.dtype], 1, N.i64_array([n]), k, ptrs,
+                                                   stride,
+                                                   None if center is None else N.ptr_array([center.data_ptr()]), c,
+                                                   m, scale, seed, round, ids, N.ptr_array([out.data_ptr()]),
+                                                   self._stream(stream))
+        N.check(rc, "fa_centered_sum_noise_tiled")
+        return out
 
     MAX_DOT_K = 128  # kMaxDotK (fedml_amd/csrc/pairdot.hip): clients per fa_pairwise_dot launch
 
