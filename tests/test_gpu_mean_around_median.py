@@ -3,13 +3,15 @@ include/fedagg_robust.h; Bulyan's second stage): bit for bit, no element left ou
 reference that follows the contract's five steps -- sort the column (NaN last, -0.0 below +0.0), take
 the lower median m = s[(K-1)/2], measure dist(v) = |v - m| in float64 (0 where v == m, +inf for NaN),
 count lo = lomin + #{r in [lomin, lomax): dist(s[r]) > dist(s[r + keep])}, sum ranks lo .. lo+keep-1
-in order in float64 from the first, divide, round once per format -- on every network bucket, both
-sides of the one-lane / two-lane and two-lane / generic boundaries, all dtypes, ragged and unaligned
-segments, the tiled and the client-major arena, hand-made columns with stated results, and against
-the trimmed mean where the two operators coincide.
+in order in float64 from the first, divide, round once per format -- on the one-lane buckets
+B = 8 .. 40, 56 and 64 and the two-lane ones N = 36, 48, 52 and 64 in float32 (16-bit types: K = 3, 6,
+32, 40, 96), both sides of the one-lane / two-lane and two-lane / generic boundaries, all dtypes, ragged
+and unaligned segments, the tiled and the client-major arena, hand-made columns with stated results, and
+against the trimmed mean where the two operators coincide.  Both ends of EVERY bucket, in every dtype
+and on inputs whose sums depend on their order, are tests/test_gpu_column_buckets.py's.
 
-The reference sorts with ``numpy.sort`` and repairs the order of -0.0 and +0.0, which ``numpy.sort``
-leaves unspecified, as tests/test_gpu_trimmed_mean.py does (``_order_zeros``).
+The reference (tests/trimcases.py) sorts with ``numpy.sort`` and repairs the order of -0.0 and +0.0, which
+``numpy.sort`` leaves unspecified (``_order_zeros``).
 
 Two data recipes.  "light" is the trimmed-mean test's (5 % each of -0.0 and +0.0, 2 % half-integer
 ties, 0.1 % NaN, 1 % +-inf); it almost never makes a median infinite.  "heavy" rewrites the columns
@@ -26,10 +28,11 @@ import numpy as np
 import pytest
 import torch
 
+from trimcases import _column_data, _heavy, _keeps, _mam, _sorted_columns, assert_same, mam_ref
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-INT_VIEW = {8: torch.int64, 4: torch.int32, 2: torch.int16}
 
 
 @pytest.fixture(scope="module")
@@ -38,111 +41,7 @@ def eng():
     return get_engine(0)
 
 
-# ----------------------------------------------------------------------------- the reference
-def _order_zeros(s, a):
-    """s: the columns of ``a`` sorted ascending along axis 0 (NaN last).  The zeros of a column are one
-    block that starts after its negatives; give the block's first rows the column's -0.0s."""
-    zero = s == 0
-    start = (s < 0).sum(axis=0)
-    nneg = ((a == 0) & np.signbit(a)).sum(axis=0)
-    r = np.arange(s.shape[0]).reshape((-1,) + (1,) * (s.ndim - 1))
-    s[zero & (r < start + nneg)] = -0.0
-    s[zero & (r >= start + nneg)] = 0.0
-    return s
-
-
-def _sorted_columns(xs):
-    dt = xs[0].dtype
-    a = torch.stack([x.to(torch.float64 if dt == torch.float64 else torch.float32) for x in xs]).numpy()
-    return _order_zeros(np.sort(a, axis=0), a)
-
-
-def _window(s, keep):
-    """Steps 2-4 on sorted columns s [K, n]: (m, lo) per column."""
-    K = s.shape[0]
-    h = (K - 1) // 2
-    m = s[h]
-    s64, m64 = s.astype(np.float64), s[h].astype(np.float64)
-    with np.errstate(all="ignore"):
-        d = np.abs(s64 - m64[None])
-    d[s == m[None]] = 0.0
-    d[np.isnan(s)] = np.inf
-    lomin, lomax = max(0, h - keep + 1), min(h, K - keep)
-    lo = np.full(s.shape[1], lomin, dtype=np.int64)
-    for r in range(lomin, lomax):
-        lo += d[r] > d[r + keep]
-    return m, lo
-
-
-def _mam(s, keep, dt):
-    m, lo = _window(s, keep)
-    cols = np.arange(s.shape[1])
-    acc = s[lo, cols].astype(np.float64)
-    with np.errstate(all="ignore"):
-        for i in range(1, keep):
-            acc = acc + s[lo + i, cols].astype(np.float64)
-        q = acc / float(keep)
-    q[np.isnan(m)] = np.nan
-    q = torch.from_numpy(q)
-    return q if dt == torch.float64 else q.to(torch.float32).to(dt)
-
-
-def mam_ref(xs, keep):
-    return _mam(_sorted_columns(xs), keep, xs[0].dtype)
-
-
-def assert_same(got, exp, what=""):
-    got, exp = got.cpu(), exp.cpu()
-    assert got.dtype == exp.dtype and got.shape == exp.shape, what
-    gn, en = torch.isnan(got), torch.isnan(exp)
-    assert torch.equal(gn, en), f"{what}: NaN positions differ in {int((gn != en).sum())} elements"
-    iv = INT_VIEW[got.element_size()]
-    bad = (got.view(iv) != exp.view(iv)) & ~en
-    if bool(bad.any()):
-        i = int(bad.flatten().nonzero()[0])
-        raise AssertionError(f"{what}: {int(bad.sum())} of {got.numel()} elements differ, first at {i}: "
-                             f"got {got.flatten()[i].item()!r}, expected {exp.flatten()[i].item()!r}")
-
-
-# ----------------------------------------------------------------------------- the data
-NEG_NAN = torch.tensor([-4194304], dtype=torch.int32).view(torch.float32).item()  # 0xFFC00000
-
-
-def _column_data(g, k, n, dtype, zeros=0.05):
-    xs = []
-    for i in range(k):
-        v = torch.randn(n, generator=g, dtype=torch.float64)
-        u = torch.rand(n, generator=g)
-        v = torch.where(u < zeros, torch.zeros_like(v), v)
-        v = torch.where((u >= zeros) & (u < 2 * zeros), -torch.zeros_like(v), v)
-        v = torch.where((u >= 0.5) & (u < 0.52), torch.round(v * 2) / 2, v)  # ties
-        v = torch.where((u >= 0.9) & (u < 0.901), torch.full_like(v, float("nan")), v)
-        v = torch.where((u >= 0.95) & (u < 0.96), torch.full_like(v, float("inf")) * torch.sign(v - 0.1), v)
-        xs.append(v.to(dtype))
-    return xs
-
-
-def _heavy(g, xs):
-    """Rewrites the columns e % 16 in 0..4 of the light data ``xs`` (in place is avoided: new tensors)."""
-    k, n = len(xs), xs[0].numel()
-    m = torch.stack([x.to(torch.float64) for x in xs])  # [k, n]
-    e = torch.arange(n)
-    # per column: a random subset of c > k/2 clients (all of them when k < 2)
-    rank = torch.rand(k, n, generator=g).argsort(dim=0).argsort(dim=0)
-    c = k // 2 + 1 + (torch.rand(n, generator=g) * (k - k // 2)).long().clamp(max=k - k // 2 - 1)
-    most = rank < c[None]
-    m = torch.where(most & (e % 16 == 0)[None], torch.full_like(m, float("inf")), m)
-    m = torch.where(most & (e % 16 == 1)[None], torch.full_like(m, float("-inf")), m)
-    m = torch.where(most & (e % 16 == 2)[None], torch.full_like(m, float("nan")), m)
-    m = torch.where((e % 16 == 3)[None], m[:1].nan_to_num(1.25, 2.5, -2.5).expand(k, n), m)
-    two = torch.where(torch.rand(k, n, generator=g) < 0.5, torch.full_like(m, -0.75), torch.full_like(m, 3.5))
-    m = torch.where((e % 16 == 4)[None], two, m)
-    out = [row.to(xs[0].dtype).contiguous() for row in m]
-    if xs[0].dtype == torch.float32:  # some of the NaNs with the sign bit set
-        neg = (rank % 2 == 1) & (e % 16 == 2)[None] & most
-        for i in range(k):
-            out[i] = torch.where(neg[i], torch.full_like(out[i], NEG_NAN), out[i])
-    return out
+# the reference, the two data recipes and _keeps: tests/trimcases.py
 
 
 @functools.lru_cache(maxsize=3)
@@ -153,10 +52,6 @@ def _case(seed, k, n, dtype, recipe):
     if recipe == "heavy":
         xs = _heavy(g, xs)
     return [x.to(DEV) for x in xs], _sorted_columns(xs), xs
-
-
-def _keeps(k):
-    return sorted({c for c in (1, 2, 3, k // 2, k - 1, k, k - 2 * (k // 5)) if 1 <= c <= k})
 
 
 def test_heavy_recipe_has_what_it_promises():
@@ -170,7 +65,7 @@ def test_heavy_recipe_has_what_it_promises():
     assert int(np.isfinite(s[h]).sum()) > 12000
 
 
-# ----------------------------------------------------------------------------- 1. float32, every bucket
+# ----------------------------------------------------------------------------- 1. float32, K across the buckets
 F32_K = [1, 2, 3, 4, 5, 7, 8, 9, 16, 17, 24, 25, 32, 33, 40, 56, 57, 63, 64, 65, 72, 96, 100, 127, 128, 129, 150]
 
 

@@ -14,6 +14,7 @@ import torch
 
 from golden_io import ROBUST_PREFIXES, client_dicts, expected_dicts, list_cases, load_case
 from refcases import assert_dict_bits, bits_equal
+from trimcases import _column_data, _special_columns
 
 pytestmark = pytest.mark.gpu
 
@@ -48,20 +49,6 @@ def test_median_defense_golden(path, where):
     out = d.defend_on_aggregation(raw)
     assert out is cl[0]  # client 0's dict, modified in place (reference :36-44)
     assert_dict_bits(OrderedDict((k, v.cpu()) for k, v in out.items()), expected_dicts(meta, arrays)[0], meta["name"])
-
-
-def _column_data(g, k, n, dtype, zeros=0.05):
-    xs = []
-    for i in range(k):
-        v = torch.randn(n, generator=g, dtype=torch.float64)
-        u = torch.rand(n, generator=g)
-        v = torch.where(u < zeros, torch.zeros_like(v), v)
-        v = torch.where((u >= zeros) & (u < 2 * zeros), -torch.zeros_like(v), v)
-        v = torch.where((u >= 0.5) & (u < 0.52), torch.round(v * 2) / 2, v)  # ties
-        v = torch.where((u >= 0.9) & (u < 0.901), torch.full_like(v, float("nan")), v)
-        v = torch.where((u >= 0.95) & (u < 0.96), torch.full_like(v, float("inf")) * torch.sign(v - 0.1), v)
-        xs.append(v.to(dtype))
-    return xs
 
 
 @pytest.mark.parametrize("k", [1, 2, 3, 4, 5, 7, 8, 9, 16, 17, 31, 32, 33, 63, 64, 65, 100, 127, 128, 129, 150])
@@ -151,33 +138,6 @@ def test_median_two_lanes_per_column(eng, dtype, k):
         exp = orc.coord_median(c)
         iv = torch.int32 if dtype == torch.float32 else torch.int16
         assert torch.equal(o.cpu().view(iv), exp.view(iv))
-
-
-def _special_columns(g, k, n, dtype):
-    """Columns mixing normal values with the bit patterns a float-key network could mishandle:
-    subnormals of both signs (denormal flushing would change the selected bits), signalling and
-    negative / payload NaNs, +-0, +-inf and the largest finite values."""
-    fb = dtype
-    if dtype == torch.float32:
-        pats = [0x00000001, 0x007FFFFF, 0x80000001, 0x807FFFFF, 0x00400000, 0x80400000, 0x7F800001, 0xFFC00000,
-                0x7FC12345, 0x00000000, 0x80000000, 0x7F800000, 0xFF800000, 0x7F7FFFFF, 0xFF7FFFFF]
-    elif dtype == torch.bfloat16:
-        pats = [0x0001, 0x007F, 0x8001, 0x807F, 0x0040, 0x7F81, 0xFFC0, 0x0000, 0x8000, 0x7F80, 0xFF80, 0x7F7F, 0xFF7F]
-    else:
-        pats = [0x0001, 0x03FF, 0x8001, 0x83FF, 0x0200, 0x7C01, 0xFE00, 0x0000, 0x8000, 0x7C00, 0xFC00, 0x7BFF, 0xFBFF]
-    w = (np.uint32, np.int32) if dtype == torch.float32 else (np.uint16, np.int16)
-    pats = torch.from_numpy(np.array(pats, dtype=w[0]).view(w[1]))
-    xs = []
-    for i in range(k):
-        v = (torch.randn(n, generator=g) * 1e-3).to(fb)
-        u = torch.rand(n, generator=g)
-        # most columns: subnormals / extremes only (no NaN) so the network, not the rescan, selects
-        sel = torch.randint(0, len(pats), (n,), generator=g)
-        special = pats[sel].view(fb)
-        nan = (special != special)
-        pick = (u < 0.6) & ~nan | (u < 0.002)
-        xs.append(torch.where(pick, special, v))
-    return xs
 
 
 @pytest.mark.parametrize("layout", ["lanes1", "lanes2", "packed"])

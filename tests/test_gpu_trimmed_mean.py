@@ -1,11 +1,13 @@
 """GPU parity of the coordinate-wise trimmed mean (fa_coord_trimmed_mean, include/fedagg_robust.h):
 bit for bit against a CPU reference that follows the contract -- sort the column (NaN last), sum the
-kept ranks in order in float64 from the first kept value, divide, round once per format -- on every
-network bucket, the one-lane / two-lane boundary, the generic kernel, all dtypes, ragged and unaligned
-segments, the tiled arena layout, hand-made columns, and through ClientArena, the defense class and
-ServerAggregator.
+kept ranks in order in float64 from the first kept value, divide, round once per format -- on the
+one-lane buckets B = 8 .. 40 and 64 and the two-lane ones N = 36, 48, 52 and 64 in float32 (16-bit
+types: K = 3, 6, 32, 40, 96), the one-lane / two-lane boundary, the generic kernel, all dtypes, ragged
+and unaligned segments, the tiled arena layout, hand-made columns, and through ClientArena, the defense
+class and ServerAggregator.  Both ends of EVERY bucket, in every dtype and on inputs whose sums depend on
+their order, are tests/test_gpu_column_buckets.py's.
 
-The reference sorts with ``numpy.sort`` and then repairs one thing: ``numpy.sort`` leaves the order of -0.0 and +0.0
+The reference (tests/trimcases.py) sorts with ``numpy.sort`` and then repairs one thing: ``numpy.sort`` leaves the order of -0.0 and +0.0
 unspecified (they compare equal; its vectorised float32 sort has even been seen to return +0.0 for
 a -0.0 input), and the kept window CAN cut through a block of zeros (odd K with b = (K-1)/2 keeps
 one value; three of the zeros -0, -0, -0, +0 sum to -0 or +0).  ``_order_zeros`` rewrites each sorted
@@ -22,75 +24,17 @@ import numpy as np
 import pytest
 import torch
 
+from trimcases import INT_VIEW, _column_data, _sorted_columns, _walk, assert_same, trimmed_mean_ref
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-INT_VIEW = {8: torch.int64, 4: torch.int32, 2: torch.int16}
 
 
 @pytest.fixture(scope="module")
 def eng():
     from fedml_amd.engine import get_engine
     return get_engine(0)
-
-
-def _order_zeros(s, a):
-    """s: the columns of ``a`` sorted ascending along axis 0 (NaN last).  The zeros of a column are one
-    block that starts after its negatives; give the block's first rows the column's -0.0s."""
-    zero = s == 0
-    start = (s < 0).sum(axis=0)
-    nneg = ((a == 0) & np.signbit(a)).sum(axis=0)
-    r = np.arange(s.shape[0]).reshape((-1,) + (1,) * (s.ndim - 1))
-    s[zero & (r < start + nneg)] = -0.0
-    s[zero & (r >= start + nneg)] = 0.0
-    return s
-
-
-def _sorted_columns(xs):
-    dt = xs[0].dtype
-    a = torch.stack([x.to(torch.float64 if dt == torch.float64 else torch.float32) for x in xs]).numpy()
-    return _order_zeros(np.sort(a, axis=0), a)
-
-
-def _walk(s, b, dt):
-    K = s.shape[0]
-    acc = s[b].astype(np.float64).copy()
-    with np.errstate(all="ignore"):
-        for r in range(b + 1, K - b):
-            acc += s[r].astype(np.float64)
-        q = torch.from_numpy(acc / float(K - 2 * b))
-    return q if dt == torch.float64 else q.to(torch.float32).to(dt)
-
-
-def trimmed_mean_ref(xs, b):
-    return _walk(_sorted_columns(xs), b, xs[0].dtype)
-
-
-def assert_same(got, exp, what=""):
-    got, exp = got.cpu(), exp.cpu()
-    assert got.dtype == exp.dtype and got.shape == exp.shape, what
-    gn, en = torch.isnan(got), torch.isnan(exp)
-    assert torch.equal(gn, en), f"{what}: NaN positions differ in {int((gn != en).sum())} elements"
-    iv = INT_VIEW[got.element_size()]
-    bad = (got.view(iv) != exp.view(iv)) & ~en
-    if bool(bad.any()):
-        i = int(bad.flatten().nonzero()[0])
-        raise AssertionError(f"{what}: {int(bad.sum())} of {got.numel()} elements differ, first at {i}: "
-                             f"got {got.flatten()[i].item()!r}, expected {exp.flatten()[i].item()!r}")
-
-
-def _column_data(g, k, n, dtype, zeros=0.05):
-    xs = []
-    for i in range(k):
-        v = torch.randn(n, generator=g, dtype=torch.float64)
-        u = torch.rand(n, generator=g)
-        v = torch.where(u < zeros, torch.zeros_like(v), v)
-        v = torch.where((u >= zeros) & (u < 2 * zeros), -torch.zeros_like(v), v)
-        v = torch.where((u >= 0.5) & (u < 0.52), torch.round(v * 2) / 2, v)  # ties
-        v = torch.where((u >= 0.9) & (u < 0.901), torch.full_like(v, float("nan")), v)
-        v = torch.where((u >= 0.95) & (u < 0.96), torch.full_like(v, float("inf")) * torch.sign(v - 0.1), v)
-        xs.append(v.to(dtype))
-    return xs
 
 
 @functools.lru_cache(maxsize=4)
@@ -104,7 +48,7 @@ def _trims(k, cands):
     return sorted({b for b in cands if 0 <= b and 2 * b < k})
 
 
-# ----------------------------------------------------------------------------- 1. float32, every bucket
+# ----------------------------------------------------------------------------- 1. float32, K across the buckets
 F32_K = [1, 2, 3, 4, 5, 7, 8, 9, 16, 17, 31, 32, 33, 40, 63, 64, 65, 72, 96, 100, 127, 128, 129, 150]
 
 
