@@ -12,7 +12,6 @@ alone unaligned.  KS cover one client, the group-of-8 boundary and the clamped l
 from __future__ import annotations
 
 import copy
-import math
 import os
 import sys
 import types
@@ -22,6 +21,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from adaptcases import f32, restate, weighted_avg  # noqa: E402,F401
 from test_gpu_geometric_median import DEV, coefs, normal_data, same_bits, segments, tiled_buf  # noqa: E402
 
 from fedml_amd import _native as N  # noqa: E402
@@ -43,60 +43,6 @@ GUARD = 7.0
 def eng():
     from fedml_amd.engine import get_engine
     return get_engine(0)
-
-
-def f32(x):
-    """A host scalar cast double -> float once."""
-    return torch.tensor(float(x), dtype=torch.float64).float()
-
-
-def weighted_avg(x, coef):
-    """fa_weighted_sum's FA_MODE_MUL_W arithmetic: clients in order, t_i = rnd(x_i * (float)coef_i)."""
-    cf = torch.tensor(list(coef), dtype=torch.float64).float()
-    avg = None
-    for i in range(x.shape[0]):
-        t = x[i] * cf[i]
-        avg = t if avg is None else avg + t
-    return avg
-
-
-def restate(x, coef, p, m, v, rule, lr, beta1, beta2, eps, wd=0.0, bias=False, step=1):
-    """One round of the contract in include/fedagg.h with torch CPU float32 ops, one op per line:
-    x [k, n], p, m (None exactly when beta1 == 0) and v [n].  Returns the new (p, m, v)."""
-    avg = weighted_avg(x, coef)
-    g = p - avg
-    if wd != 0:
-        pw = p * f32(wd)
-        g = g + pw
-    g2 = g * g
-    if rule == ADAM:
-        a = v * f32(beta2)
-        b = g2 * f32(1 - beta2)
-        v = a + b
-    elif rule == YOGI:
-        d = v - g2
-        s = (d > 0).float() - (d < 0).float()  # a NaN: neither comparison holds
-        t = f32(1 - beta2) * g2
-        t = t * s
-        v = v - t
-    else:
-        v = v + g2
-    if beta1 != 0:
-        a = m * f32(beta1)
-        b = g * f32(1 - beta1)
-        m = a + b
-        num = m
-    else:
-        num = g
-    c2 = f32(math.sqrt(1 - beta2 ** step)) if bias else f32(1.0)
-    step_size = f32(lr / (1 - beta1 ** step) if bias else lr)
-    root = v.double().sqrt().float()
-    den = root / c2
-    den = den + f32(eps)
-    q = num / den
-    q = step_size * q
-    p = p - q
-    return p, m, v
 
 
 def place(flat, sizes, offset):
