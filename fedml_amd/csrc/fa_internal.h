@@ -53,10 +53,16 @@ __device__ __forceinline__ int64_t xcd_tile_map(int64_t bid, int64_t tiles) {
 int fail(int code, const char* fmt, ...);
 const char* last_error();
 
+// The failure is reported here, once: HIP also keeps it as the thread's last error, which the next
+// launch check of the host framework would report again as its own (a failed call here made
+// unrelated torch operations fail with its error), so it is taken off.
 #define FA_HIP(call)                                                                     \
   do {                                                                                   \
     hipError_t e_ = (call);                                                              \
-    if (e_ != hipSuccess) return ::fa_detail::fail(FA_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
+    if (e_ != hipSuccess) {                                                              \
+      (void)hipGetLastError();                                                           \
+      return ::fa_detail::fail(FA_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_));     \
+    }                                                                                    \
   } while (0)
 
 struct DeviceGuard {

@@ -1240,7 +1240,19 @@ int fa_stream_create_cu_masked(int hip_device, int cu_count, void** out_stream) 
   for (int i = 0; i < total; ++i)
     if ((int64_t)i * cu_count / total != (int64_t)(i + 1) * cu_count / total) mask[i / 32] |= 1u << (i % 32);
   hipStream_t s = nullptr;
-  FA_HIP(hipExtStreamCreateWithCUMask(&s, (uint32_t)words, mask));
+  const hipError_t e = hipExtStreamCreateWithCUMask(&s, (uint32_t)words, mask);
+  if (e != hipSuccess) {
+    // A device that takes no CU mask (a GPU handed to a virtual machine: the masked queue is refused
+    // with hipErrorOutOfMemory): an ordinary stream of the same kind.  The results are the same;
+    // no CUs are set aside, which matters only beside RCCL's kernels on a multi-GPU round.
+    (void)hipGetLastError();
+    static std::atomic<bool> told{false};
+    if (!told.exchange(true))
+      fprintf(stderr, "libfedagg: no CU-masked streams on this device (hipExtStreamCreateWithCUMask: %s); "
+              "fa_stream_create_cu_masked returns unmasked streams\n", hipGetErrorString(e));
+    s = nullptr;
+    FA_HIP(hipStreamCreateWithFlags(&s, hipStreamDefault));
+  }
   *out_stream = (void*)s;
   return FA_OK;
 }

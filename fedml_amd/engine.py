@@ -112,7 +112,8 @@ class AggEngine:
 
     def cu_masked_stream(self, cu_count: int) -> torch.cuda.ExternalStream:
         """A torch stream whose kernels run on ``cu_count`` CUs of this device
-        (fa_stream_create_cu_masked); kept alive for the engine's lifetime."""
+        (fa_stream_create_cu_masked); kept alive for the engine's lifetime.  Where the device
+        refuses CU masks (inside a virtual machine) it is an ordinary stream over all CUs."""
         h = N.ctypes.c_void_p()
         N.check(self._lib.fa_stream_create_cu_masked(self.device_index, int(cu_count), N.ctypes.byref(h)),
                 "fa_stream_create_cu_masked")

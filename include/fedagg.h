@@ -319,7 +319,9 @@ int fa_ctx_set_mix_band(fa_ctx *ctx, int enable);
  * A HIP stream restricted to `cu_count` of the device's CUs (spread evenly over the CU mask).
  * Launch the aggregation on it during multi-GPU rounds: the HBM stream saturates with about half
  * of the CUs, and the others stay free for the RCCL collective running beside it.  Destroy with
- * fa_stream_destroy.  Not part of the arithmetic contract.
+ * fa_stream_destroy.  Not part of the arithmetic contract.  On a device that refuses CU-masked
+ * queues (a GPU inside a virtual machine) the stream is an ordinary one over all CUs, and the
+ * library says so once on stderr: the same results, no CUs set aside.
  */
 int fa_stream_create_cu_masked(int hip_device, int cu_count, void **out_stream);
 int fa_stream_destroy(void *stream);
