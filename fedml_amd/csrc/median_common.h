@@ -73,7 +73,7 @@ struct MSeg {
   void* out;
   int64_t tstride;  // 0: flat client segments; > 0: tile-interleaved inputs, bytes between a client's tiles
   int32_t ptr_base;
-  int32_t aligned;  // every input and the output are 16-byte aligned (read by wsum_dist.hip only)
+  int32_t aligned;  // every input and the output are 16-byte aligned (read by wsum_dist.hip and signbits.hip)
 };
 static_assert(sizeof(MSeg) == 40, "MSeg layout");
 

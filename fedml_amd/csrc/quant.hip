@@ -24,8 +24,8 @@
 #include "elem.h"
 #include "fa_internal.h"
 #include "fedagg_quant.h"
+#include "blockq_host.h"
 #include "median_common.h"
-#include "median_host.h"
 
 using namespace fa_detail;
 
@@ -39,7 +39,7 @@ constexpr int kUE = 2;  // the same on the byte path (16 q and 16 scale register
 
 using G4 = __attribute__((address_space(1))) u32x4;
 
-enum { kQAligned = 1, kOutAligned = 2 };  // per-segment flags of k_wsum_q8
+constexpr int kQAligned = kDataAligned;  // per-segment flags of k_wsum_q8: blockq_host.h's
 
 __device__ __forceinline__ float q8_coef(float scale, const double* __restrict__ coef, int i, bool mulw) {
   return mulw ? op_mul(scale, (float)coef[i]) : scale;
@@ -262,83 +262,20 @@ k_quantize_q8(const MSeg* __restrict__ segs, int nseg, const void* const* __rest
   else q8_quant_slot<DT, false>(sg, tl, in, scale, shift);
 }
 
-// log2 of a valid block size, or -1
-int q8_shift(int32_t block) {
-  if (block < FA_Q8_BLOCK_MIN || block > FA_Q8_BLOCK_MAX || (block & (block - 1))) return -1;
-  int s = 0;
-  while ((1 << s) < block) ++s;
-  return s;
-}
-inline bool al4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
+constexpr BlockFmt kQ8{"q", FA_Q8_BLOCK_MIN, FA_Q8_BLOCK_MAX, 0};
 
 }  // namespace
 
+// The argument checks, the staged tables and the payload are blockq_host.h's, shared with signbits.hip.
 extern "C" {
 
 int fa_weighted_sum_q8(fa_ctx* ctx, int mode, int32_t num_segments, const int64_t* seg_numel, int32_t k, int32_t block,
                        const void* const* d_q, const void* const* d_scale, const double* coef, void* const* d_out,
                        void* hip_stream) {
-  const char* fn = "fa_weighted_sum_q8";
-  if (!ctx) return fail(FA_ERR_INVALID, "%s: ctx is NULL", fn);
-  const int shift = q8_shift(block);
-  if (shift < 0)
-    return fail(FA_ERR_INVALID, "%s: block %d is not a power of two in [%d, %d]", fn, block, FA_Q8_BLOCK_MIN,
-                FA_Q8_BLOCK_MAX);
-  if (k <= 0 || num_segments <= 0) return fail(FA_ERR_INVALID, "%s: k and num_segments must be positive", fn);
-  if (!seg_numel || !d_q || !d_scale || !d_out) return fail(FA_ERR_INVALID, "%s: a table is NULL", fn);
-  if (!coef && mode != FA_MODE_SUM) return fail(FA_ERR_INVALID, "%s: coef is NULL (allowed for FA_MODE_SUM only)", fn);
-  if (mode != FA_MODE_MUL_W && mode != FA_MODE_SUM)
-    return fail(FA_ERR_DTYPE, "%s: mode %d not supported (FA_MODE_MUL_W, FA_MODE_SUM)", fn, mode);
-  int nseg = 0;
-  int64_t tiles = 0;
-  for (int s = 0; s < num_segments; ++s) {
-    if (seg_numel[s] < 0) return fail(FA_ERR_INVALID, "%s: segment %d has negative numel", fn, s);
-    if (seg_numel[s] == 0) continue;
-    if (!d_out[s] || !al4(d_out[s]))
-      return fail(FA_ERR_INVALID, "%s: segment %d: output NULL or not 4-byte aligned", fn, s);
-    for (int i = 0; i < k; ++i) {
-      const int64_t t = (int64_t)s * k + i;
-      if (!d_q[t]) return fail(FA_ERR_INVALID, "%s: segment %d client %d: q NULL", fn, s, i);
-      if (!d_scale[t] || !al4(d_scale[t]))
-        return fail(FA_ERR_INVALID, "%s: segment %d client %d: scale NULL or not 4-byte aligned", fn, s, i);
-    }
-    ++nseg;
-    tiles += (seg_numel[s] + E - 1) / E;
-  }
-  if (tiles > 0x7FFFFFFFll) return fail(FA_ERR_INVALID, "%s: too many tiles", fn);
-  if (nseg == 0) return FA_OK;
-
-  // the payload: the k coefficients, the non-empty segments' scale pointers ([segment][client], as
-  // the q table), and one flag word per segment
-  const ColArgs a{fn, ctx, FA_DTYPE_F32, num_segments, seg_numel, k, d_q, 0, d_out, hip_stream};
-  const size_t coef_bytes = sizeof(double) * (size_t)k;
-  const size_t ptr_bytes = sizeof(void*) * (size_t)nseg * k;
-  const size_t fl_off = coef_bytes + ptr_bytes;
-  const size_t extra = fl_off + ((sizeof(int) * (size_t)nseg + 7) & ~size_t(7));
-  return col_stage_launch(
-      a, E, nseg, tiles, extra,
-      [&](void* h) {
-        for (int i = 0; i < k; ++i) ((double*)h)[i] = coef ? coef[i] : 0.0;
-        const void** hs = (const void**)((char*)h + coef_bytes);
-        int* hfl = (int*)((char*)h + fl_off);
-        int j = 0;
-        for (int s = 0; s < num_segments; ++s) {
-          if (!seg_numel[s]) continue;
-          bool qal = true;
-          for (int i = 0; i < k; ++i) {
-            hs[(int64_t)j * k + i] = d_scale[(int64_t)s * k + i];
-            qal = qal && al16(d_q[(int64_t)s * k + i]);
-          }
-          hfl[j] = (qal ? kQAligned : 0) | (al16(d_out[s]) ? kOutAligned : 0);
-          ++j;
-        }
-        if (nseg & 1) hfl[nseg] = 0;  // the padding is staged too
-      },
-      [&](dim3 grid, hipStream_t st, const MSeg* ds, int n, const void* const* dp, const void* payload) {
-        const char* pl = (const char*)payload;
-        const double* dc = (const double*)pl;
-        const void* const* dsc = (const void* const*)(pl + coef_bytes);
-        const int* dfl = (const int*)(pl + fl_off);
+  return block_sum_entry(
+      "fa_weighted_sum_q8", kQ8, E, ctx, mode, num_segments, seg_numel, k, block, d_q, d_scale, coef, d_out, hip_stream,
+      [&](dim3 grid, hipStream_t st, const MSeg* ds, int n, const void* const* dp, const void* const* dsc,
+          const int* dfl, const double* dc, int shift) {
         const dim3 blk(kBlock);
         if (mode == FA_MODE_MUL_W) hipLaunchKernelGGL((k_wsum_q8<true>), grid, blk, 0, st, ds, n, dp, dsc, dfl, dc, k, shift);
         else hipLaunchKernelGGL((k_wsum_q8<false>), grid, blk, 0, st, ds, n, dp, dsc, dfl, dc, k, shift);
@@ -347,43 +284,9 @@ int fa_weighted_sum_q8(fa_ctx* ctx, int mode, int32_t num_segments, const int64_
 
 int fa_quantize_q8(fa_ctx* ctx, int dtype, int32_t num_segments, const int64_t* seg_numel, int32_t block,
                    const void* const* d_in, void* const* d_q, void* const* d_scale, void* hip_stream) {
-  const char* fn = "fa_quantize_q8";
-  if (!ctx) return fail(FA_ERR_INVALID, "%s: ctx is NULL", fn);
-  const int shift = q8_shift(block);
-  if (shift < 0)
-    return fail(FA_ERR_INVALID, "%s: block %d is not a power of two in [%d, %d]", fn, block, FA_Q8_BLOCK_MIN,
-                FA_Q8_BLOCK_MAX);
-  if (num_segments <= 0) return fail(FA_ERR_INVALID, "%s: num_segments must be positive", fn);
-  if (!seg_numel || !d_in || !d_q || !d_scale) return fail(FA_ERR_INVALID, "%s: a table is NULL", fn);
-  if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_BF16 && dtype != FA_DTYPE_F16)
-    return fail(FA_ERR_DTYPE, "%s: dtype %d not supported (F32, BF16, F16)", fn, dtype);
-  const uintptr_t in_mask = dtype == FA_DTYPE_F32 ? 3u : 1u;
-  int nseg = 0;
-  int64_t tiles = 0;
-  for (int s = 0; s < num_segments; ++s) {
-    if (seg_numel[s] < 0) return fail(FA_ERR_INVALID, "%s: segment %d has negative numel", fn, s);
-    if (seg_numel[s] == 0) continue;
-    if (!d_in[s] || ((uintptr_t)d_in[s] & in_mask))
-      return fail(FA_ERR_INVALID, "%s: segment %d: input NULL or not aligned to its element", fn, s);
-    if (!d_q[s]) return fail(FA_ERR_INVALID, "%s: segment %d: q NULL", fn, s);
-    if (!d_scale[s] || !al4(d_scale[s]))
-      return fail(FA_ERR_INVALID, "%s: segment %d: scale NULL or not 4-byte aligned", fn, s);
-    ++nseg;
-    tiles += (seg_numel[s] + E - 1) / E;
-  }
-  if (tiles > 0x7FFFFFFFll) return fail(FA_ERR_INVALID, "%s: too many tiles", fn);
-  if (nseg == 0) return FA_OK;
-
-  // the table: one "client" per segment (the input), the output is q; the payload: the scale pointers
-  const ColArgs a{fn, ctx, dtype, num_segments, seg_numel, 1, d_in, 0, d_q, hip_stream};
-  return col_stage_launch(
-      a, E, nseg, tiles, sizeof(void*) * (size_t)nseg,
-      [&](void* h) {
-        for (int s = 0, j = 0; s < num_segments; ++s)
-          if (seg_numel[s]) ((void**)h)[j++] = d_scale[s];
-      },
-      [&](dim3 grid, hipStream_t st, const MSeg* ds, int n, const void* const* dp, const void* payload) {
-        void* const* dsc = (void* const*)payload;
+  return block_quant_entry(
+      "fa_quantize_q8", kQ8, E, ctx, dtype, num_segments, seg_numel, block, d_in, d_q, d_scale, hip_stream,
+      [&](dim3 grid, hipStream_t st, const MSeg* ds, int n, const void* const* dp, void* const* dsc, int shift) {
         const dim3 blk(kBlock);
         switch (dtype) {
           case FA_DTYPE_F32: hipLaunchKernelGGL((k_quantize_q8<FA_DTYPE_F32>), grid, blk, 0, st, ds, n, dp, dsc, shift); break;

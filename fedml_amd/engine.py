@@ -996,6 +996,146 @@ class AggEngine:
         N.check(rc, "fa_weighted_sum_q8")
         return results
 
+    # ------------------------------------------------------------------ 1-bit sign compression (q1)
+    @staticmethod
+    def _check_q1_block(what: str, block) -> int:
+        b = int(block)
+        if b != block or b < N.Q1_BLOCK_MIN or b > N.Q1_BLOCK_MAX or b & (b - 1):
+            raise ValueError(f"{what}: block {block!r} must be a power of two in "
+                             f"[{N.Q1_BLOCK_MIN}, {N.Q1_BLOCK_MAX}]")
+        return b
+
+    def quantize_q1(self, xs: Sequence[torch.Tensor], block: int = 128,
+                    outs: Optional[Tuple[Sequence[torch.Tensor], Sequence[torch.Tensor]]] = None,
+                    stream=None) -> Tuple[List[torch.Tensor], List[torch.Tensor]]:
+        """Sign-compress same-dtype device tensors (float32, bfloat16 or float16) to the q1 format of
+        include/fedagg_sign.h in one launch (fa_quantize_q1).  Returns (bits, scales): bits[s] is int32
+        with ceil(numel / 32) words, scales[s] is float32 with ceil(numel / block) elements.  ``outs``:
+        (bits, scales) to write into."""
+        block = self._check_q1_block("quantize_q1", block)
+        if len(xs) == 0:
+            return [], []
+        dt = xs[0].dtype
+        if dt not in (torch.float32, torch.bfloat16, torch.float16):
+            raise TypeError(f"quantize_q1: unsupported dtype {dt} (float32, bfloat16, float16)")
+        bits, scales = [], []
+        for s, t in enumerate(xs):
+            if t.dtype != dt:
+                raise TypeError(f"quantize_q1: tensor {s} is {t.dtype}, expected {dt}")
+            _require_device(t, self.device, f"tensor {s}")
+            nw, nb = -(-t.numel() // 32), -(-t.numel() // block)
+            if outs is not None:
+                b, sc = outs[0][s], outs[1][s]
+                if b.dtype != torch.int32 or b.numel() != nw:
+                    raise ValueError(f"quantize_q1: bits output {s} must be int32 with {nw} words")
+                if sc.dtype != torch.float32 or sc.numel() != nb:
+                    raise ValueError(f"quantize_q1: scale output {s} must be float32 with {nb} elements")
+                _require_device(b, self.device, f"bits output {s}")
+                _require_device(sc, self.device, f"scale output {s}")
+            else:
+                b = torch.empty(nw, dtype=torch.int32, device=self.device)
+                sc = torch.empty(nb, dtype=torch.float32, device=self.device)
+            bits.append(b)
+            scales.append(sc)
+        rc = self._lib.fa_quantize_q1(
+            self._ctx, DTYPE_CODE[dt], len(xs), N.i64_array([t.numel() for t in xs]), block,
+            N.ptr_array([t.data_ptr() for t in xs]), N.ptr_array([b.data_ptr() for b in bits]),
+            N.ptr_array([sc.data_ptr() for sc in scales]), self._stream(stream))
+        N.check(rc, "fa_quantize_q1")
+        return bits, scales
+
+    def _q1_bits_table(self, what: str, bits_segments, numels) -> Tuple[int, List[int]]:
+        """Validates bits_segments[s][i] (int32, ceil(numels[s] / 32) words, on the device); returns
+        (k, the pointer table [s * k + i])."""
+        if len(bits_segments) != len(numels):
+            raise ValueError(f"{what}: bits_segments and numels differ in length")
+        k = len(bits_segments[0])
+        if k == 0:
+            raise ValueError(f"{what}: no client tensors")
+        ptrs = []
+        for s, (seg, n) in enumerate(zip(bits_segments, numels)):
+            if len(seg) != k:
+                raise ValueError(f"segment {s}: {len(seg)} bits tensors, expected {k}")
+            for i, b in enumerate(seg):
+                if b.dtype != torch.int32:
+                    raise TypeError(f"segment {s} client {i}: bits must be int32 (got {b.dtype})")
+                if b.numel() != -(-int(n) // 32):
+                    raise ValueError(f"segment {s} client {i}: {b.numel()} words, expected {-(-int(n) // 32)} "
+                                     f"for {n} elements")
+                _require_device(b, self.device, f"segment {s} client {i} bits")
+                ptrs.append(b.data_ptr())
+        return k, ptrs
+
+    def _q1_outs(self, numels, outs) -> List[torch.Tensor]:
+        if outs is None:
+            return [torch.empty(int(n), dtype=torch.float32, device=self.device) for n in numels]
+        if len(outs) != len(numels):
+            raise ValueError(f"{len(outs)} outputs for {len(numels)} segments")
+        for s, (o, n) in enumerate(zip(outs, numels)):
+            if o.dtype != torch.float32 or o.numel() != n:
+                raise ValueError(f"segment {s}: output must be float32 with {n} elements")
+            _require_device(o, self.device, f"segment {s} output")
+        return list(outs)
+
+    def weighted_sum_q1(self, bits_segments: Sequence[Sequence[torch.Tensor]],
+                        scale_segments: Sequence[Sequence[torch.Tensor]], numels: Sequence[int], mode: int,
+                        coef: Optional[Sequence[float]] = None, block: int = 128,
+                        outs: Optional[Sequence[torch.Tensor]] = None, stream=None) -> List[torch.Tensor]:
+        """Fused decompress-and-sum of q1 client tensors (fa_weighted_sum_q1), one launch:
+        bits_segments[s][i] / scale_segments[s][i] = client i's int32 bit words and float32 scales for
+        key s, numels[s] its element count.  ``mode`` is MUL_W (``coef`` = the weights) or SUM.  Returns
+        one flat float32 tensor per key.  k = 1 with SUM decompresses."""
+        block = self._check_q1_block("weighted_sum_q1", block)
+        if len(bits_segments) != len(scale_segments):
+            raise ValueError("weighted_sum_q1: bits_segments and scale_segments differ in length")
+        if len(bits_segments) == 0:
+            return []
+        if mode not in (MUL_W, SUM):
+            raise ValueError(f"weighted_sum_q1: mode {mode} not supported (MUL_W, SUM)")
+        k, b_ptrs = self._q1_bits_table("weighted_sum_q1", bits_segments, numels)
+        if mode != SUM and (coef is None or len(coef) != k):
+            raise ValueError("weighted_sum_q1: need one coefficient per client")
+        s_ptrs = []
+        for s, (sseg, n) in enumerate(zip(scale_segments, numels)):
+            nb = -(-int(n) // block)
+            if len(sseg) != k:
+                raise ValueError(f"segment {s}: {len(sseg)} scale tensors, expected {k}")
+            for i, sc in enumerate(sseg):
+                if sc.dtype != torch.float32:
+                    raise TypeError(f"segment {s} client {i}: scale must be float32 (got {sc.dtype})")
+                if sc.numel() != nb:
+                    raise ValueError(f"segment {s} client {i}: {sc.numel()} scales, expected {nb} "
+                                     f"for {n} elements in blocks of {block}")
+                _require_device(sc, self.device, f"segment {s} client {i} scale")
+                s_ptrs.append(sc.data_ptr())
+        results = self._q1_outs(numels, outs)
+        rc = self._lib.fa_weighted_sum_q1(
+            self._ctx, int(mode), len(numels), N.i64_array(numels), k, block, N.ptr_array(b_ptrs),
+            N.ptr_array(s_ptrs), N.f64_array(coef) if mode != SUM else None,
+            N.ptr_array([o.data_ptr() for o in results]), self._stream(stream))
+        N.check(rc, "fa_weighted_sum_q1")
+        return results
+
+    def sign_vote_q1(self, bits_segments: Sequence[Sequence[torch.Tensor]], numels: Sequence[int],
+                     threshold: int = 1, step: float = 1.0, outs: Optional[Sequence[torch.Tensor]] = None,
+                     stream=None) -> List[torch.Tensor]:
+        """Majority vote over the clients' sign bits (fa_sign_vote_q1), one launch: per element
+        net = (#clear bits) - (#set bits); +step where net >= threshold, -step where net <= -threshold,
+        +0 otherwise.  Returns one flat float32 tensor per key."""
+        if len(bits_segments) == 0:
+            return []
+        k, b_ptrs = self._q1_bits_table("sign_vote_q1", bits_segments, numels)
+        if k > N.Q1_VOTE_MAX_K:
+            raise ValueError(f"sign_vote_q1: {k} clients, at most {N.Q1_VOTE_MAX_K}")
+        if int(threshold) != threshold or not 1 <= threshold <= k:
+            raise ValueError(f"sign_vote_q1: threshold {threshold!r} must be an integer in [1, {k}]")
+        results = self._q1_outs(numels, outs)
+        rc = self._lib.fa_sign_vote_q1(
+            self._ctx, len(numels), N.i64_array(numels), k, N.ptr_array(b_ptrs), int(threshold), float(step),
+            N.ptr_array([o.data_ptr() for o in results]), self._stream(stream))
+        N.check(rc, "fa_sign_vote_q1")
+        return results
+
     def lcc_decode(self, coef: Sequence[Sequence[int]], f: torch.Tensor, prime: int, n_out: int,
                    stream=None) -> torch.Tensor:
         """First n_out entries of np.mod(coef.dot(f), p) (int64 wrap), f an int64 (k x m) device tensor."""

@@ -21,6 +21,7 @@ from collections import OrderedDict
 from typing import List, Tuple
 
 from .quantized import Q8Tensor, aggregate_q8
+from .signcompressed import Q1Tensor, aggregate_q1, majority_vote_q1
 from .state_dict_agg import MUL_W, SUM, aggregate
 
 # args.ml_engine values (python/fedml/core/common/ml_engine_backend.py)
@@ -61,9 +62,36 @@ def _q8_aggregator(args, raw_grad_list, training_num):
                               "for FedAvg, FedProx, FedAvg_seq and FedDyn only")
 
 
+def _holds_q1(raw_grad_list) -> bool:
+    """Client 0's dicts hold a sign-compressed tensor (signcompressed.Q1Tensor): the round is a q1 round."""
+    if not raw_grad_list:
+        return False
+    return any(isinstance(v, Q1Tensor) for d in raw_grad_list[0][1:] if isinstance(d, dict) for v in d.values())
+
+
+def _q1_aggregator(args, raw_grad_list, training_num):
+    """1-bit sign-compressed uploads (not in the reference): with args.q1_majority_vote the majority vote
+    (args.q1_vote_threshold, default 1; args.q1_vote_step, default 1.0), else the FedAvg / FedProx
+    weighted sum and the FedAvg_seq / FedDyn plain sum on the fused decompress-and-sum kernel."""
+    opt = args.federated_optimizer
+    if opt not in ("FedAvg", "FedProx", "FedAvg_seq", "FedDyn"):
+        raise NotImplementedError(f"federated_optimizer={opt!r}: sign-compressed (Q1Tensor) state_dicts are "
+                                  "aggregated for FedAvg, FedProx, FedAvg_seq and FedDyn only")
+    dicts = [p for _, p in raw_grad_list]
+    if any(isinstance(v, Q8Tensor) for d in dicts for v in d.values()):
+        raise TypeError("a round mixes Q8Tensor and Q1Tensor values: one compressed format per round")
+    if getattr(args, "q1_majority_vote", False):
+        return majority_vote_q1(dicts, getattr(args, "q1_vote_threshold", 1), getattr(args, "q1_vote_step", 1.0))
+    if opt in ("FedAvg", "FedProx"):
+        return aggregate_q1(dicts, MUL_W, [n / training_num for n, _ in raw_grad_list])
+    return aggregate_q1(dicts, SUM)
+
+
 def torch_aggregator(args, raw_grad_list, training_num):
     """Reference: agg_operator.py:33-134, one branch per federated optimizer."""
     opt = args.federated_optimizer
+    if _holds_q1(raw_grad_list):
+        return _q1_aggregator(args, raw_grad_list, training_num)
     if _holds_q8(raw_grad_list):
         return _q8_aggregator(args, raw_grad_list, training_num)
     if opt in ("FedAvg", "FedProx"):
