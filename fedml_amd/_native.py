@@ -58,12 +58,17 @@ QUANT_SYMBOLS = ("fa_quantize_q8", "fa_weighted_sum_q8")
 DP_SYMBOLS = ("fa_noise_words", "fa_add_noise", "fa_centered_sum_noise", "fa_centered_sum_noise_tiled")
 # include/fedagg_sign.h (the 1-bit sign-compressed entries; checked by lib() like EXPORTED_SYMBOLS)
 SIGN_SYMBOLS = ("fa_quantize_q1", "fa_weighted_sum_q1", "fa_sign_vote_q1")
+# include/fedagg_mx.h (the Microscaling entries; checked by lib() like EXPORTED_SYMBOLS)
+MX_SYMBOLS = ("fa_quantize_mx", "fa_weighted_sum_mx")
 NOISE_GAUSSIAN, NOISE_LAPLACE = 0, 1  # enum fa_noise_mech
 NOISE_Z_ABS_ERR = 2.4e-6              # FA_NOISE_Z_ABS_ERR
 Q8_BLOCK_MIN, Q8_BLOCK_MAX = 16, 1024  # FA_Q8_BLOCK_MIN / FA_Q8_BLOCK_MAX
 Q1_BLOCK_MIN, Q1_BLOCK_MAX = 32, 1024  # FA_Q1_BLOCK_MIN / FA_Q1_BLOCK_MAX
 Q1_VOTE_MAX_K = 4095                   # FA_Q1_VOTE_MAX_K
 Q1_SUM_SLOT, Q1_VOTE_SLOT, Q1_GROUP = 8192, 32768, 8  # FA_Q1_SUM_SLOT / FA_Q1_VOTE_SLOT / FA_Q1_GROUP
+MX_FP8, MX_FP4 = 0, 1                  # enum fa_mx_format
+MX_BLOCK = 32                          # FA_MX_BLOCK
+MX_FP8_SLOT, MX_FP4_SLOT, MX_GROUP = 4096, 8192, 8  # FA_MX_FP8_SLOT / FA_MX_FP4_SLOT / FA_MX_GROUP
 
 # enum fa_exchange / fa_local_kind (include/fedagg_comm.h)
 XCHG_ORDERED, XCHG_ORDERED_ALL, XCHG_REDUCE, XCHG_ALL_REDUCE, XCHG_REDUCE_SCATTER = 0, 1, 2, 3, 4
@@ -309,6 +314,11 @@ def _declare(L):
     L.fa_sign_vote_q1.restype = ctypes.c_int
     L.fa_sign_vote_q1.argtypes = [_vp, ctypes.c_int32, _P_i64, ctypes.c_int32, _P_vp, ctypes.c_int32, ctypes.c_double,
                                   _P_vp, _vp]
+    L.fa_quantize_mx.restype = ctypes.c_int
+    L.fa_quantize_mx.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int32, _P_i64, _P_vp, _P_vp, _P_vp, _vp]
+    L.fa_weighted_sum_mx.restype = ctypes.c_int
+    L.fa_weighted_sum_mx.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int32, _P_i64, ctypes.c_int32,
+                                     _P_vp, _P_vp, _P_d, _P_vp, _vp]
     L.fa_noise_words.restype = ctypes.c_int
     L.fa_noise_words.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64,
                                  ctypes.c_int64, _vp, _vp]
@@ -343,7 +353,8 @@ def lib():
             L = ctypes.CDLL(LIB_PATH)
         except OSError as e:
             raise FedAggNativeError(f"cannot load {LIB_PATH}: {e}") from e
-        missing = [s for s in EXPORTED_SYMBOLS + QUANT_SYMBOLS + DP_SYMBOLS + SIGN_SYMBOLS if not hasattr(L, s)]
+        missing = [s for s in EXPORTED_SYMBOLS + QUANT_SYMBOLS + DP_SYMBOLS + SIGN_SYMBOLS + MX_SYMBOLS
+                   if not hasattr(L, s)]
         if missing:
             raise FedAggNativeError(f"{LIB_PATH} lacks symbols {missing}")
         _declare(L)

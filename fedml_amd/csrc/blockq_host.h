@@ -1,7 +1,8 @@
 // blockq_host.h -- the host path shared by the block-compressed client formats: q8 (quant.hip, one
 // int8 per element) and q1 (signbits.hip, one sign bit per element), both with one float32 scale per
-// block of B elements.  The two entries of a format differ only in the names in their messages, the
-// block range, the alignment their data needs and the kernel they launch; the argument checks (in the
+// block of B elements, and mx (mx.hip, one FP8 or FP4 code per element with one E8M0 scale byte per
+// block of 32).  The two entries of a format differ only in the names in their messages, the block
+// range, the alignment their data and scales need and the kernel they launch; the argument checks (in the
 // order the headers state), the staged tables and the payload are the same and live here once.
 // Not part of the ABI.
 #pragma once
@@ -16,9 +17,10 @@ inline bool al4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
 
 // What tells one format from the other on the host.
 struct BlockFmt {
-  const char* data;      // the data table's name in the messages ("q", "bits")
+  const char* data;      // the data table's name in the messages ("q", "bits", "data")
   int block_min, block_max;
   uintptr_t data_mask;   // alignment the data pointers need, as a mask (0: any)
+  uintptr_t scale_mask = 3;  // the same for the scale pointers: float32 scales 3, mx's scale bytes 0
 };
 
 // log2 of a valid block size, or -1
@@ -35,13 +37,15 @@ inline int block_fail(const char* fn, const BlockFmt& f, int32_t block) {
 
 inline bool data_ok(const BlockFmt& f, const void* p) { return p && !((uintptr_t)p & f.data_mask); }
 inline const char* data_what(const BlockFmt& f) { return f.data_mask ? " or not 4-byte aligned" : ""; }
+inline bool scale_ok(const BlockFmt& f, const void* p) { return p && !((uintptr_t)p & f.scale_mask); }
+inline const char* scale_what(const BlockFmt& f) { return f.scale_mask ? " or not 4-byte aligned" : ""; }
 
 // The fused decompress-and-sum of k clients: d_data[s * k + i], d_scale[s * k + i], d_out[s]; a
 // workgroup owns `slot` elements.  Checks in the order of fedagg_quant.h / fedagg_sign.h, then stages
 // the MSeg and data-pointer tables and, as the payload, the k coefficients, the non-empty segments'
 // scale pointers ([segment][client], as the data table) and one flag word per segment, and calls
 // launch(grid, stream, segs, nseg, data ptrs, scale ptrs, flags, coef, shift).  kDataAligned is staged for
-// both formats; only q8 reads it (k_wsum_q1 loads one dword per lane, the same at any 4-byte alignment).
+// every format; q8 and mx read it (k_wsum_q1 loads one dword per lane, the same at any 4-byte alignment).
 template <class Launch>
 int block_sum_entry(const char* fn, const BlockFmt& f, int64_t slot, fa_ctx* ctx, int mode, int32_t num_segments,
                     const int64_t* seg_numel, int32_t k, int32_t block, const void* const* d_data,
@@ -66,8 +70,8 @@ int block_sum_entry(const char* fn, const BlockFmt& f, int64_t slot, fa_ctx* ctx
       const int64_t t = (int64_t)s * k + i;
       if (!data_ok(f, d_data[t]))
         return fail(FA_ERR_INVALID, "%s: segment %d client %d: %s NULL%s", fn, s, i, f.data, data_what(f));
-      if (!d_scale[t] || !al4(d_scale[t]))
-        return fail(FA_ERR_INVALID, "%s: segment %d client %d: scale NULL or not 4-byte aligned", fn, s, i);
+      if (!scale_ok(f, d_scale[t]))
+        return fail(FA_ERR_INVALID, "%s: segment %d client %d: scale NULL%s", fn, s, i, scale_what(f));
     }
     ++nseg;
     tiles += (seg_numel[s] + slot - 1) / slot;
@@ -130,8 +134,7 @@ int block_quant_entry(const char* fn, const BlockFmt& f, int64_t slot, fa_ctx* c
     if (!d_in[s] || ((uintptr_t)d_in[s] & in_mask))
       return fail(FA_ERR_INVALID, "%s: segment %d: input NULL or not aligned to its element", fn, s);
     if (!data_ok(f, d_data[s])) return fail(FA_ERR_INVALID, "%s: segment %d: %s NULL%s", fn, s, f.data, data_what(f));
-    if (!d_scale[s] || !al4(d_scale[s]))
-      return fail(FA_ERR_INVALID, "%s: segment %d: scale NULL or not 4-byte aligned", fn, s);
+    if (!scale_ok(f, d_scale[s])) return fail(FA_ERR_INVALID, "%s: segment %d: scale NULL%s", fn, s, scale_what(f));
     ++nseg;
     tiles += (seg_numel[s] + slot - 1) / slot;
   }

@@ -1066,7 +1066,7 @@ class AggEngine:
                 ptrs.append(b.data_ptr())
         return k, ptrs
 
-    def _q1_outs(self, numels, outs) -> List[torch.Tensor]:
+    def _f32_outs(self, numels, outs) -> List[torch.Tensor]:
         if outs is None:
             return [torch.empty(int(n), dtype=torch.float32, device=self.device) for n in numels]
         if len(outs) != len(numels):
@@ -1108,7 +1108,7 @@ class AggEngine:
                                      f"for {n} elements in blocks of {block}")
                 _require_device(sc, self.device, f"segment {s} client {i} scale")
                 s_ptrs.append(sc.data_ptr())
-        results = self._q1_outs(numels, outs)
+        results = self._f32_outs(numels, outs)
         rc = self._lib.fa_weighted_sum_q1(
             self._ctx, int(mode), len(numels), N.i64_array(numels), k, block, N.ptr_array(b_ptrs),
             N.ptr_array(s_ptrs), N.f64_array(coef) if mode != SUM else None,
@@ -1129,11 +1129,105 @@ class AggEngine:
             raise ValueError(f"sign_vote_q1: {k} clients, at most {N.Q1_VOTE_MAX_K}")
         if int(threshold) != threshold or not 1 <= threshold <= k:
             raise ValueError(f"sign_vote_q1: threshold {threshold!r} must be an integer in [1, {k}]")
-        results = self._q1_outs(numels, outs)
+        results = self._f32_outs(numels, outs)
         rc = self._lib.fa_sign_vote_q1(
             self._ctx, len(numels), N.i64_array(numels), k, N.ptr_array(b_ptrs), int(threshold), float(step),
             N.ptr_array([o.data_ptr() for o in results]), self._stream(stream))
         N.check(rc, "fa_sign_vote_q1")
+        return results
+
+    # ------------------------------------------------------------------ OCP Microscaling (mx)
+    @staticmethod
+    def _mx_format(what: str, fmt) -> Tuple[int, int]:
+        """(FA_MX_* code, elements per data byte) of "fp8" / "fp4"."""
+        if fmt not in ("fp8", "fp4"):
+            raise ValueError(f'{what}: fmt {fmt!r} must be "fp8" or "fp4"')
+        return (N.MX_FP8, 1) if fmt == "fp8" else (N.MX_FP4, 2)
+
+    def quantize_mx(self, xs: Sequence[torch.Tensor], fmt: str,
+                    outs: Optional[Tuple[Sequence[torch.Tensor], Sequence[torch.Tensor]]] = None,
+                    stream=None) -> Tuple[List[torch.Tensor], List[torch.Tensor]]:
+        """Quantize same-dtype device tensors (float32, bfloat16 or float16) to the MXFP8 ("fp8") or MXFP4
+        ("fp4") format of include/fedagg_mx.h in one launch (fa_quantize_mx).  Returns (data, scales):
+        data[s] is flat uint8 with numel (fp8) or ceil(numel / 2) (fp4) bytes, scales[s] is uint8 with
+        ceil(numel / 32) E8M0 bytes.  ``outs``: (data, scales) to write into."""
+        code, epb = self._mx_format("quantize_mx", fmt)
+        if len(xs) == 0:
+            return [], []
+        dt = xs[0].dtype
+        if dt not in (torch.float32, torch.bfloat16, torch.float16):
+            raise TypeError(f"quantize_mx: unsupported dtype {dt} (float32, bfloat16, float16)")
+        data, scales = [], []
+        for s, t in enumerate(xs):
+            if t.dtype != dt:
+                raise TypeError(f"quantize_mx: tensor {s} is {t.dtype}, expected {dt}")
+            _require_device(t, self.device, f"tensor {s}")
+            nd, nb = -(-t.numel() // epb), -(-t.numel() // N.MX_BLOCK)
+            if outs is not None:
+                d, sc = outs[0][s], outs[1][s]
+                if d.dtype != torch.uint8 or d.numel() != nd:
+                    raise ValueError(f"quantize_mx: data output {s} must be uint8 with {nd} bytes")
+                if sc.dtype != torch.uint8 or sc.numel() != nb:
+                    raise ValueError(f"quantize_mx: scale output {s} must be uint8 with {nb} bytes")
+                _require_device(d, self.device, f"data output {s}")
+                _require_device(sc, self.device, f"scale output {s}")
+            else:
+                d = torch.empty(nd, dtype=torch.uint8, device=self.device)
+                sc = torch.empty(nb, dtype=torch.uint8, device=self.device)
+            data.append(d)
+            scales.append(sc)
+        rc = self._lib.fa_quantize_mx(
+            self._ctx, code, DTYPE_CODE[dt], len(xs), N.i64_array([t.numel() for t in xs]),
+            N.ptr_array([t.data_ptr() for t in xs]), N.ptr_array([d.data_ptr() for d in data]),
+            N.ptr_array([sc.data_ptr() for sc in scales]), self._stream(stream))
+        N.check(rc, "fa_quantize_mx")
+        return data, scales
+
+    def weighted_sum_mx(self, data_segments: Sequence[Sequence[torch.Tensor]],
+                        scale_segments: Sequence[Sequence[torch.Tensor]], numels: Sequence[int], fmt: str,
+                        mode: int, coef: Optional[Sequence[float]] = None,
+                        outs: Optional[Sequence[torch.Tensor]] = None, stream=None) -> List[torch.Tensor]:
+        """Fused decode-and-sum of MX client tensors (fa_weighted_sum_mx), one launch:
+        data_segments[s][i] / scale_segments[s][i] = client i's uint8 element bytes and E8M0 scale bytes for
+        key s, numels[s] its element count.  ``mode`` is MUL_W (``coef`` = the weights) or SUM.  Returns one
+        flat float32 tensor per key.  k = 1 with SUM decodes."""
+        code, epb = self._mx_format("weighted_sum_mx", fmt)
+        if len(data_segments) != len(scale_segments) or len(data_segments) != len(numels):
+            raise ValueError("weighted_sum_mx: data_segments, scale_segments and numels differ in length")
+        if len(data_segments) == 0:
+            return []
+        k = len(data_segments[0])
+        if k == 0:
+            raise ValueError("weighted_sum_mx: no client tensors")
+        if mode not in (MUL_W, SUM):
+            raise ValueError(f"weighted_sum_mx: mode {mode} not supported (MUL_W, SUM)")
+        if mode != SUM and (coef is None or len(coef) != k):
+            raise ValueError("weighted_sum_mx: need one coefficient per client")
+        d_ptrs, s_ptrs = [], []
+        for s, (dseg, sseg, n) in enumerate(zip(data_segments, scale_segments, numels)):
+            if len(dseg) != k or len(sseg) != k:
+                raise ValueError(f"segment {s}: {len(dseg)} data and {len(sseg)} scale tensors, expected {k}")
+            nd, nb = -(-int(n) // epb), -(-int(n) // N.MX_BLOCK)
+            for i, (d, sc) in enumerate(zip(dseg, sseg)):
+                if d.dtype != torch.uint8 or sc.dtype != torch.uint8:
+                    raise TypeError(f"segment {s} client {i}: data and scale must be uint8 "
+                                    f"(got {d.dtype}, {sc.dtype})")
+                if d.numel() != nd:
+                    raise ValueError(f"segment {s} client {i}: {d.numel()} data bytes, expected {nd} "
+                                     f"for {n} {fmt} elements")
+                if sc.numel() != nb:
+                    raise ValueError(f"segment {s} client {i}: {sc.numel()} scale bytes, expected {nb} "
+                                     f"for {n} elements in blocks of {N.MX_BLOCK}")
+                _require_device(d, self.device, f"segment {s} client {i} data")
+                _require_device(sc, self.device, f"segment {s} client {i} scale")
+                d_ptrs.append(d.data_ptr())
+                s_ptrs.append(sc.data_ptr())
+        results = self._f32_outs(numels, outs)
+        rc = self._lib.fa_weighted_sum_mx(
+            self._ctx, code, int(mode), len(numels), N.i64_array(numels), k, N.ptr_array(d_ptrs),
+            N.ptr_array(s_ptrs), N.f64_array(coef) if mode != SUM else None,
+            N.ptr_array([o.data_ptr() for o in results]), self._stream(stream))
+        N.check(rc, "fa_weighted_sum_mx")
         return results
 
     def lcc_decode(self, coef: Sequence[Sequence[int]], f: torch.Tensor, prime: int, n_out: int,

@@ -20,6 +20,7 @@ import logging
 from collections import OrderedDict
 from typing import List, Tuple
 
+from .microscaled import MXTensor, aggregate_mx
 from .quantized import Q8Tensor, aggregate_q8
 from .signcompressed import Q1Tensor, aggregate_q1, majority_vote_q1
 from .state_dict_agg import MUL_W, SUM, aggregate
@@ -87,9 +88,33 @@ def _q1_aggregator(args, raw_grad_list, training_num):
     return aggregate_q1(dicts, SUM)
 
 
+def _holds_mx(raw_grad_list) -> bool:
+    """Client 0's dicts hold a Microscaling tensor (microscaled.MXTensor): the round is an mx round."""
+    if not raw_grad_list:
+        return False
+    return any(isinstance(v, MXTensor) for d in raw_grad_list[0][1:] if isinstance(d, dict) for v in d.values())
+
+
+def _mx_aggregator(args, raw_grad_list, training_num):
+    """MXFP8 / MXFP4 uploads (not in the reference): the FedAvg / FedProx weighted sum and the FedAvg_seq /
+    FedDyn plain sum on the fused decode-and-sum kernel.  aggregate_mx rejects a round of both formats."""
+    opt = args.federated_optimizer
+    if opt not in ("FedAvg", "FedProx", "FedAvg_seq", "FedDyn"):
+        raise NotImplementedError(f"federated_optimizer={opt!r}: Microscaling (MXTensor) state_dicts are "
+                                  "aggregated for FedAvg, FedProx, FedAvg_seq and FedDyn only")
+    dicts = [p for _, p in raw_grad_list]
+    if any(isinstance(v, (Q8Tensor, Q1Tensor)) for d in dicts for v in d.values()):
+        raise TypeError("a round mixes MXTensor with Q8Tensor or Q1Tensor values: one compressed format per round")
+    if opt in ("FedAvg", "FedProx"):
+        return aggregate_mx(dicts, MUL_W, [n / training_num for n, _ in raw_grad_list])
+    return aggregate_mx(dicts, SUM)
+
+
 def torch_aggregator(args, raw_grad_list, training_num):
     """Reference: agg_operator.py:33-134, one branch per federated optimizer."""
     opt = args.federated_optimizer
+    if _holds_mx(raw_grad_list):
+        return _mx_aggregator(args, raw_grad_list, training_num)
     if _holds_q1(raw_grad_list):
         return _q1_aggregator(args, raw_grad_list, training_num)
     if _holds_q8(raw_grad_list):
