@@ -60,6 +60,8 @@ DP_SYMBOLS = ("fa_noise_words", "fa_add_noise", "fa_centered_sum_noise", "fa_cen
 SIGN_SYMBOLS = ("fa_quantize_q1", "fa_weighted_sum_q1", "fa_sign_vote_q1")
 # include/fedagg_mx.h (the Microscaling entries; checked by lib() like EXPORTED_SYMBOLS)
 MX_SYMBOLS = ("fa_quantize_mx", "fa_weighted_sum_mx")
+# include/fedagg_rotate.h (the randomized Hadamard rotation; checked by lib() like EXPORTED_SYMBOLS)
+ROTATE_SYMBOLS = ("fa_hadamard_rotate",)
 NOISE_GAUSSIAN, NOISE_LAPLACE = 0, 1  # enum fa_noise_mech
 NOISE_Z_ABS_ERR = 2.4e-6              # FA_NOISE_Z_ABS_ERR
 Q8_BLOCK_MIN, Q8_BLOCK_MAX = 16, 1024  # FA_Q8_BLOCK_MIN / FA_Q8_BLOCK_MAX
@@ -69,6 +71,9 @@ Q1_SUM_SLOT, Q1_VOTE_SLOT, Q1_GROUP = 8192, 32768, 8  # FA_Q1_SUM_SLOT / FA_Q1_V
 MX_FP8, MX_FP4 = 0, 1                  # enum fa_mx_format
 MX_BLOCK = 32                          # FA_MX_BLOCK
 MX_FP8_SLOT, MX_FP4_SLOT, MX_GROUP = 4096, 8192, 8  # FA_MX_FP8_SLOT / FA_MX_FP4_SLOT / FA_MX_GROUP
+RHT_LOG2_MIN, RHT_LOG2_MAX = 5, 13     # FA_RHT_LOG2_MIN / FA_RHT_LOG2_MAX
+RHT_FORWARD, RHT_INVERSE = 0, 1        # enum fa_rht_direction
+RHT_SLOT = 8192                        # FA_RHT_SLOT
 
 # enum fa_exchange / fa_local_kind (include/fedagg_comm.h)
 XCHG_ORDERED, XCHG_ORDERED_ALL, XCHG_REDUCE, XCHG_ALL_REDUCE, XCHG_REDUCE_SCATTER = 0, 1, 2, 3, 4
@@ -319,6 +324,9 @@ def _declare(L):
     L.fa_weighted_sum_mx.restype = ctypes.c_int
     L.fa_weighted_sum_mx.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int32, _P_i64, ctypes.c_int32,
                                      _P_vp, _P_vp, _P_d, _P_vp, _vp]
+    L.fa_hadamard_rotate.restype = ctypes.c_int
+    L.fa_hadamard_rotate.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint32,
+                                     ctypes.c_int32, _P_i64, _P_u32, _P_vp, _P_vp, _vp]
     L.fa_noise_words.restype = ctypes.c_int
     L.fa_noise_words.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64,
                                  ctypes.c_int64, _vp, _vp]
@@ -353,7 +361,7 @@ def lib():
             L = ctypes.CDLL(LIB_PATH)
         except OSError as e:
             raise FedAggNativeError(f"cannot load {LIB_PATH}: {e}") from e
-        missing = [s for s in EXPORTED_SYMBOLS + QUANT_SYMBOLS + DP_SYMBOLS + SIGN_SYMBOLS + MX_SYMBOLS
+        missing = [s for s in EXPORTED_SYMBOLS + QUANT_SYMBOLS + DP_SYMBOLS + SIGN_SYMBOLS + MX_SYMBOLS + ROTATE_SYMBOLS
                    if not hasattr(L, s)]
         if missing:
             raise FedAggNativeError(f"{LIB_PATH} lacks symbols {missing}")

@@ -1230,6 +1230,54 @@ class AggEngine:
         N.check(rc, "fa_weighted_sum_mx")
         return results
 
+    # ------------------------------------------------------------------ randomized Hadamard rotation
+    def hadamard_rotate(self, xs: Sequence[torch.Tensor], log2_block: int, seed: int, round: int,
+                        seg_ids: Sequence[int], inverse: bool = False, numels: Optional[Sequence[int]] = None,
+                        outs: Optional[Sequence[torch.Tensor]] = None, stream=None) -> List[torch.Tensor]:
+        """The randomized Hadamard rotation of include/fedagg_rotate.h in one launch (fa_hadamard_rotate):
+        blocks of 2 ** log2_block elements, signs from (seed, round, seg_ids[s]).  Forward: same-dtype
+        device tensors (float32, bfloat16 or float16) to flat float32 tensors of n_pad elements (n rounded
+        up to whole blocks).  ``inverse``: those float32 tensors plus ``numels`` (the unpadded counts) to
+        flat float32 tensors of n elements.  ``outs``: tensors to write into."""
+        what = "hadamard_rotate"
+        b = int(log2_block)
+        if b != log2_block or not N.RHT_LOG2_MIN <= b <= N.RHT_LOG2_MAX:
+            raise ValueError(f"{what}: log2_block {log2_block!r} must be an integer in "
+                             f"[{N.RHT_LOG2_MIN}, {N.RHT_LOG2_MAX}]")
+        _, _, seed, round, ids = self._noise_args(what, 0, 0.0, seed, round, seg_ids, len(xs))
+        if len(xs) == 0:
+            return []
+        dt = xs[0].dtype
+        if inverse:
+            if dt != torch.float32:
+                raise TypeError(f"{what}: the inverse takes float32 tensors (got {dt})")
+            if numels is None or len(numels) != len(xs):
+                raise ValueError(f"{what}: the inverse needs one unpadded element count per tensor")
+            numels = [int(n) for n in numels]
+        else:
+            if dt not in (torch.float32, torch.bfloat16, torch.float16):
+                raise TypeError(f"{what}: unsupported dtype {dt} (float32, bfloat16, float16)")
+            if numels is not None:
+                raise ValueError(f"{what}: numels belongs to the inverse")
+            numels = [t.numel() for t in xs]
+        pads = [-(-n >> b) << b for n in numels]
+        for s, t in enumerate(xs):
+            if t.dtype != dt:
+                raise TypeError(f"{what}: tensor {s} is {t.dtype}, expected {dt}")
+            if not t.is_contiguous():
+                raise ValueError(f"{what}: tensor {s} is not contiguous")
+            if inverse and (numels[s] < 0 or t.numel() != pads[s]):
+                raise ValueError(f"{what}: tensor {s} has {t.numel()} elements, expected {pads[s]} "
+                                 f"for {numels[s]} elements in blocks of {1 << b}")
+            _require_device(t, self.device, f"tensor {s}")
+        results = self._f32_outs(numels if inverse else pads, outs)
+        rc = self._lib.fa_hadamard_rotate(
+            self._ctx, DTYPE_CODE[dt], N.RHT_INVERSE if inverse else N.RHT_FORWARD, b, seed, round, len(xs),
+            N.i64_array(numels), ids, N.ptr_array([t.data_ptr() for t in xs]),
+            N.ptr_array([o.data_ptr() for o in results]), self._stream(stream))
+        N.check(rc, "fa_hadamard_rotate")
+        return results
+
     def lcc_decode(self, coef: Sequence[Sequence[int]], f: torch.Tensor, prime: int, n_out: int,
                    stream=None) -> torch.Tensor:
         """First n_out entries of np.mod(coef.dot(f), p) (int64 wrap), f an int64 (k x m) device tensor."""

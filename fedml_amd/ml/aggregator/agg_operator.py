@@ -22,6 +22,7 @@ from typing import List, Tuple
 
 from .microscaled import MXTensor, aggregate_mx
 from .quantized import Q8Tensor, aggregate_q8
+from .rotated import RotatedTensor, aggregate_rotated
 from .signcompressed import Q1Tensor, aggregate_q1, majority_vote_q1
 from .state_dict_agg import MUL_W, SUM, aggregate
 
@@ -110,9 +111,38 @@ def _mx_aggregator(args, raw_grad_list, training_num):
     return aggregate_mx(dicts, SUM)
 
 
+def _holds_rotated(raw_grad_list) -> bool:
+    """Client 0's dicts hold a rotated tensor (rotated.RotatedTensor): the round is a rotated round."""
+    if not raw_grad_list:
+        return False
+    return any(isinstance(v, RotatedTensor) for d in raw_grad_list[0][1:] if isinstance(d, dict) for v in d.values())
+
+
+def _rotated_aggregator(args, raw_grad_list, training_num):
+    """Rotated uploads, plain or compressed (not in the reference): the FedAvg / FedProx weighted sum and
+    the FedAvg_seq / FedDyn plain sum in the rotated domain, the rotation undone once on the sum with
+    args.rotation_seed.  A majority vote is not linear, so it cannot be taken on rotated signs."""
+    opt = args.federated_optimizer
+    if opt not in ("FedAvg", "FedProx", "FedAvg_seq", "FedDyn"):
+        raise NotImplementedError(f"federated_optimizer={opt!r}: rotated (RotatedTensor) state_dicts are "
+                                  "aggregated for FedAvg, FedProx, FedAvg_seq and FedDyn only")
+    if getattr(args, "q1_majority_vote", False):
+        raise NotImplementedError("q1_majority_vote on rotated state_dicts: a vote is not linear, so the rotation "
+                                  "cannot be undone on its result")
+    seed = getattr(args, "rotation_seed", None)
+    if seed is None:
+        raise ValueError("rotated (RotatedTensor) state_dicts need args.rotation_seed, the round's Rotation.seed")
+    dicts = [p for _, p in raw_grad_list]
+    if opt in ("FedAvg", "FedProx"):
+        return aggregate_rotated(dicts, MUL_W, [n / training_num for n, _ in raw_grad_list], seed)
+    return aggregate_rotated(dicts, SUM, None, seed)
+
+
 def torch_aggregator(args, raw_grad_list, training_num):
     """Reference: agg_operator.py:33-134, one branch per federated optimizer."""
     opt = args.federated_optimizer
+    if _holds_rotated(raw_grad_list):
+        return _rotated_aggregator(args, raw_grad_list, training_num)
     if _holds_mx(raw_grad_list):
         return _mx_aggregator(args, raw_grad_list, training_num)
     if _holds_q1(raw_grad_list):
