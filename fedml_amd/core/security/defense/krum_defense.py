@@ -12,6 +12,12 @@ reference also rounds to that dtype (``vectorize_weight`` keeps it; the device p
 against the reference (tests/golden/g18_*, including bf16 / f16 models).  float64 models are
 measured in float64 throughout, as the reference measures them (fa_pairwise_sqdist_rt with
 FA_DTYPE_F64; g18_krum_f64_* includes a near-tie that float32 distances would order differently).
+
+Block-quantized uploads: when every weight key of every client is a `Q8Tensor` of one block size of at
+least 64, the distances come from ``fa_pairwise_gram_q8`` -- the Gram matrix straight from the int8
+bytes on the int8 matrix cores, no float32 copy of the clients -- and the selected clients' Q8 dicts
+are returned untouched for `aggregate_q8`.  Blocks of 16 or 32 (below one int8 matrix instruction) are
+dequantized key by key (``weighted_sum_q8`` with one client) and take the float32 path.
 """
 from __future__ import annotations
 
@@ -22,8 +28,14 @@ from typing import Any, List, Tuple
 import numpy as np
 import torch
 
-from ....engine import get_engine
+from ....engine import SUM, get_engine
+from ....ml.aggregator.microscaled import MXTensor
+from ....ml.aggregator.quantized import Q8Tensor
+from ....ml.aggregator.rotated import RotatedTensor
+from ....ml.aggregator.signcompressed import Q1Tensor
 from ..common.utils import is_weight_param
+
+Q8_GRAM_BLOCK_MIN = 64  # FA_Q8_GRAM_BLOCK_MIN: one v_mfma_i32_16x16x64_i8
 
 
 class KrumDefense(object):
@@ -61,6 +73,18 @@ class KrumDefense(object):
         as vectorize_weight does), one device pass; for bf16 / f16 models every difference is
         rounded to that dtype as the reference's ``v_i - v_j`` does."""
         keys = [k for k in grads[0].keys() if is_weight_param(k)]
+        q8_block = self._q8_block(grads, keys)
+        if q8_block is not None:
+            dev = next((g[k].q.device for g in grads for k in keys if g[k].q.is_cuda), None)
+            eng = get_engine(dev.index if dev is not None else None)
+            on = lambda t: t if t.device == eng.device else t.to(eng.device)  # noqa: E731
+            if q8_block >= Q8_GRAM_BLOCK_MIN:
+                _, D = eng.pairwise_gram_q8([[on(g[k].q).reshape(-1) for g in grads] for k in keys],
+                                            [[on(g[k].scale) for g in grads] for k in keys], q8_block)
+                return D.cpu().numpy()
+            # blocks of 16 or 32: the weight keys dequantized (one launch per client), then the float path
+            grads = [dict(zip(keys, eng.weighted_sum_q8([[on(g[k].q)] for k in keys], [[on(g[k].scale)] for k in keys],
+                                                        SUM, None, q8_block))) for g in grads]
         vdt = self.vector_dtype(grads)
         diff_dt = vdt if vdt in (torch.bfloat16, torch.float16, torch.float64) else torch.float32
         in_dt = torch.float64 if diff_dt == torch.float64 else torch.float32
@@ -76,6 +100,35 @@ class KrumDefense(object):
                 col.append(t.to(in_dt).contiguous().reshape(-1))
             segs.append(col)
         return eng.pairwise_sqdist(segs, diff_dtype=diff_dt).cpu().numpy()
+
+    @staticmethod
+    def _q8_block(grads, keys):
+        """The block size when every weight key of every client is a Q8Tensor, None when none is one;
+        anything else is an error."""
+        other = next((type(g[k]).__name__ for g in grads for k in keys
+                      if isinstance(g[k], (Q1Tensor, MXTensor, RotatedTensor))), None)
+        if other is not None:
+            raise TypeError(f"KrumDefense: {other} state_dicts are not supported: Krum takes plain tensors or "
+                            "block-quantized int8 (Q8Tensor) weight keys")
+        first = grads[0]
+        qset = {k for k in keys if isinstance(first[k], Q8Tensor)}
+        for i, g in enumerate(grads):
+            for k in keys:
+                if isinstance(g[k], Q8Tensor) != (k in qset):
+                    raise TypeError(f"key {k!r}: client {i} {'has' if isinstance(g[k], Q8Tensor) else 'lacks'} a "
+                                    f"Q8Tensor where client 0 {'has' if k in qset else 'lacks'} one")
+        if not qset:
+            return None
+        if len(qset) != len(keys):
+            raise TypeError("KrumDefense: plain and Q8Tensor weight keys are mixed: quantize every weight key or none")
+        block = first[keys[0]].block
+        for i, g in enumerate(grads):
+            for k in keys:
+                if g[k].block != block:
+                    raise ValueError(f"key {k!r}: client {i} block {g[k].block} != {block} (one block size per call)")
+                if g[k].shape != first[k].shape:
+                    raise ValueError(f"key {k!r}: client {i} shape {g[k].shape} != {first[k].shape}")
+        return block
 
     def _compute_krum_score(self, grads):
         D = self.pairwise_sq_distances(grads)

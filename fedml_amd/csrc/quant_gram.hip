@@ -1,0 +1,398 @@
+// quant_gram.hip -- MI355X (gfx950) kernels + C ABI of the q8 Gram matrix and pairwise squared distances
+// (include/fedagg_quant_gram.h: fa_pairwise_gram_q8): Krum's device pass straight on block-quantized int8
+// uploads.  The contract and its op order are the header's.
+//
+// G_ij = sum_b s_i[b] s_j[b] I_ij[b]: the integer part I of a block is exact in int32 on
+// v_mfma_i32_16x16x64_i8, the two scales go in through float64 with one fma per block, pair and lane.
+//
+// k_gram_q8: a workgroup (8 waves) owns a run of consecutive units (kUnit elements of one segment, all k
+// clients; the split is the header's, a function of the segment sizes alone).  It walks the run in stages
+// of W elements (W by k, so that a stage is <= 32 KB of q): the k clients' int8 rows of a stage lie in
+// LDS row-major, row stride W + 16 bytes (the 16 rows that one 16-byte operand read touches then fall in
+// 16 different bank groups), next to the stage's scales widened to float64, [block][client].  Two stages
+// in LDS: the loads of stage s + 1 are issued into registers before the MFMAs of stage s and written
+// after them, one barrier per stage.  Rows k .. 16 nt - 1 and everything past a segment's end are zero.
+// The nt (nt + 1) / 2 upper-triangular pairs of 16-client tiles are dealt to the waves round-robin
+// (pair p to wave p % 8: one pair for k <= 16, 36 pairs = at most 5 per wave for k = 128; PW, the
+// pairs per wave, is the template parameter, so every accumulator has a fixed register).  Per pair the
+// wave keeps 4 int32 and 4 float64 accumulators per lane; a block of B elements is B / 64 MFMAs into
+// the int32 ones (across stages when B > W), then one scale step: acc64 = fma(s_i s_j, (double)I, acc64).
+// Per-workgroup float64 slabs ([pair][16][16]) go to the scratch; k_gram_q8_reduce adds them in a fixed
+// order and writes both triangles of G; k_gram_q8_dist forms D from G's bits.
+// Numbers and the resource use: DESIGN.md (block-quantized family).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+
+#include "fa_internal.h"
+#include "fedagg_quant.h"
+#include "blockq_host.h"
+#include "median_common.h"
+
+using namespace fa_detail;
+
+namespace {
+
+constexpr int kGramThreads = 512, kGramWaves = kGramThreads / 64;
+constexpr int kUnit = FA_Q8_GRAM_UNIT;
+constexpr int kNI = 4;        // 16-byte items of q per thread and stage: 2,048 items = 32 KB at most
+constexpr int kPad = 16;      // bytes between the rows of a stage
+constexpr int kMaxPW = 5;     // 36 pairs on 8 waves
+// the largest of 2 * 16 nt * (W + kPad) bytes of q (nt = 4, W = 512) + 2 * max(1, W / 64) * 16 nt float64 scales
+constexpr int kGramLds = 2 * 128 * (256 + kPad) + 8192;
+static_assert(kGramLds >= 2 * 64 * (512 + kPad) + 8192 && kGramLds >= 2 * 32 * (1024 + kPad) + 8192,
+              "LDS of every plan");
+static_assert(2 * kGramLds <= 160 * 1024, "two workgroups per CU");
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+struct GSeg {
+  int64_t numel;
+  int64_t tile_start;  // first unit of this segment (find_seg keys on it)
+  int32_t ptr_base;
+  int32_t aligned;     // every q pointer of the segment is 16-byte aligned
+};
+static_assert(sizeof(GSeg) == 24, "GSeg layout");
+
+constexpr BlockFmt kQ8Gram{"q", FA_Q8_GRAM_BLOCK_MIN, FA_Q8_BLOCK_MAX, 0};
+
+struct GramPlan { int nt, npairs, pw, W; };
+GramPlan gram_plan(int k) {
+  GramPlan p;
+  p.nt = (k + 15) / 16;
+  p.npairs = p.nt * (p.nt + 1) / 2;
+  p.pw = (p.npairs + kGramWaves - 1) / kGramWaves;
+  p.W = p.nt <= 2 ? 1024 : p.nt <= 4 ? 512 : FA_Q8_GRAM_STAGE_MIN;
+  return p;
+}
+
+int64_t gram_units(int32_t num_segments, const int64_t* seg_numel) {
+  int64_t n = 0;
+  for (int s = 0; s < num_segments; ++s)
+    if (seg_numel[s] > 0) n += (seg_numel[s] + kUnit - 1) / kUnit;
+  return n;
+}
+int64_t gram_workgroups(int64_t units) {
+  return std::min<int64_t>(FA_Q8_GRAM_MAX_WORKGROUPS, (units + FA_Q8_GRAM_MIN_UNITS - 1) / FA_Q8_GRAM_MIN_UNITS);
+}
+
+// pair -> (ti, tj), ti <= tj: row-major over the upper triangle of nt tiles
+__device__ __forceinline__ void pair_tiles(int p, int nt, int& ti, int& tj) {
+  int r = 0, rem = p;
+  while (rem >= nt - r) { rem -= nt - r; ++r; }
+  ti = r;
+  tj = r + rem;
+}
+
+template <int PW>
+__global__ void __launch_bounds__(kGramThreads)
+k_gram_q8(const GSeg* __restrict__ segs, int nseg, const void* const* __restrict__ qptrs,
+          const void* const* __restrict__ sptrs, int k, int nt, int W, int shift, int64_t nunits,
+          double* __restrict__ partial) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[kGramLds];
+  const int R = 16 * nt, S = W + kPad, B = 1 << shift;
+  const int nbs = (W >> shift) > 0 ? (W >> shift) : 1;  // blocks (or the one part of a block) per stage
+  unsigned char* lq = smem;                      // [2][R][S]
+  double* lsc = (double*)(smem + 2 * R * S);     // [2][nbs][R]
+  const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int npairs = nt * (nt + 1) / 2;
+
+  // staging roles, the same in every stage: item n is 16 bytes of client irow[n]; one scale per thread
+  const int C = W / 16;
+  int irow[kNI], icol[kNI];
+  bool iact[kNI];
+#pragma unroll
+  for (int n = 0; n < kNI; ++n) {
+    const int idx = t + n * kGramThreads;
+    irow[n] = idx / C;
+    icol[n] = idx % C;
+    iact[n] = irow[n] < k;
+  }
+  const bool sact = t < nbs * R && t % R < k;
+  const int sblk = t / R, srow = t % R;
+
+  // rows k .. R - 1 of both buffers, q and scales, are zero; no stage writes them
+  for (int idx = t; idx < 2 * (R - k) * (S / 4); idx += kGramThreads) {
+    const int b = idx / ((R - k) * (S / 4)), r = idx / (S / 4) % (R - k), c = idx % (S / 4);
+    ((unsigned*)lq)[((b * R + k + r) * S) / 4 + c] = 0u;
+  }
+  for (int idx = t; idx < 2 * nbs * R; idx += kGramThreads)
+    if (idx % R >= k) lsc[idx] = 0.0;
+
+  // the loader's position: unit lu of segment sg, stage at element le0 of the segment
+  const int64_t u0 = nunits * blockIdx.x / gridDim.x, u1 = nunits * (blockIdx.x + 1) / gridDim.x;
+  int64_t lu = u0, le0 = 0;
+  int cseg = -1;
+  GSeg sg{};
+  const void* qp[kNI];
+  const void* sp = nullptr;
+  auto enter_unit = [&]() {
+    const int sidx = nseg > 1 ? find_seg(segs, nseg, lu) : 0;
+    if (sidx != cseg) {  // one set of pointer loads per segment
+      cseg = sidx;
+      sg = segs[sidx];
+#pragma unroll
+      for (int n = 0; n < kNI; ++n) qp[n] = iact[n] ? qptrs[sg.ptr_base + irow[n]] : nullptr;
+      sp = sact ? sptrs[sg.ptr_base + srow] : nullptr;
+    }
+    le0 = (lu - sg.tile_start) * kUnit;
+  };
+  auto advance = [&]() {  // to the next stage of the unit that starts inside the segment, or the next unit
+    le0 += W;
+    if ((le0 & (kUnit - 1)) == 0 || le0 >= sg.numel) {
+      ++lu;
+      if (lu < u1) enter_unit();
+    }
+  };
+  u32x4 rq[kNI];
+  double rs = 0.0;
+  auto load = [&]() {
+#pragma unroll
+    for (int n = 0; n < kNI; ++n) {
+      rq[n] = u32x4{0u, 0u, 0u, 0u};
+      if (!iact[n]) continue;
+      const int64_t e = le0 + 16 * icol[n], left = sg.numel - e;
+      if (left >= 16 && sg.aligned) {
+        rq[n] = __builtin_nontemporal_load((const __attribute__((address_space(1))) u32x4*)((const char*)qp[n] + e));
+      } else if (left > 0) {  // byte loads: the same 16 bytes, zeros past the segment's end
+#pragma unroll
+        for (int v = 0; v < 16; ++v)
+          if (v < left) rq[n][v / 4] |= (unsigned)gld<unsigned char>(qp[n], e + v) << (8 * (v % 4));
+      }
+    }
+    if (sact) {
+      const int64_t b = (le0 >> shift) + sblk, nblk = (sg.numel + B - 1) >> shift;
+      rs = b < nblk ? (double)gld<float>(sp, b) : 0.0;
+    }
+  };
+  auto put = [&](int buf) {
+#pragma unroll
+    for (int n = 0; n < kNI; ++n)
+      if (iact[n]) *(u32x4*)(lq + (buf * R + irow[n]) * S + 16 * icol[n]) = rq[n];
+    if (sact) lsc[(buf * nbs + sblk) * R + srow] = rs;
+  };
+
+  // the wave's pairs
+  int pti[PW], ptj[PW];
+  i32x4 iacc[PW];
+  double dacc[PW][4];
+#pragma unroll
+  for (int u = 0; u < PW; ++u) {
+    pti[u] = ptj[u] = 0;
+    if (wave + u * kGramWaves < npairs) pair_tiles(wave + u * kGramWaves, nt, pti[u], ptj[u]);
+    iacc[u] = i32x4{0, 0, 0, 0};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dacc[u][r] = 0.0;
+  }
+  // v_mfma_i32_16x16x64_i8, D = A B + C with A 16 x 64, B 64 x 16 (int8) and C, D 16 x 16 (int32):
+  //   A: lane l holds row l % 16, 16 consecutive k of the 64 in its 4 VGPRs, the group chosen by l / 16;
+  //   B: lane l holds column l % 16, the same k group;
+  //   D: lane l, VGPR r holds D[4 (l / 16) + r][l % 16].
+  // Both operands are read from the same 16 bytes, 16 (l / 16) .. + 15 of the 64-element step, of their
+  // client's row, so every k meets itself whichever order the hardware gives the 16 bytes of a group.
+  const int kq = lane >> 4, lr = lane & 15;
+  auto compute = [&](int buf, int64_t e0, int64_t numel) {
+#pragma unroll
+    for (int u = 0; u < PW; ++u) {
+      if (wave + u * kGramWaves >= npairs) continue;  // wave-uniform
+      const unsigned char* pa = lq + (buf * R + 16 * pti[u] + lr) * S + 16 * kq;
+      const unsigned char* pb = lq + (buf * R + 16 * ptj[u] + lr) * S + 16 * kq;
+      for (int j = 0; j < W; j += 64) {
+        const i32x4 a = *(const i32x4*)(pa + j), b = *(const i32x4*)(pb + j);
+        iacc[u] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, iacc[u], 0, 0, 0);
+        const int64_t e = e0 + j + 64;
+        if ((e & (B - 1)) == 0 || e >= numel) {  // the block ends here: its scale step
+          const double* sc = lsc + (buf * nbs + (j >> shift)) * R;
+          const double sj = sc[16 * ptj[u] + lr];
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            dacc[u][r] = __builtin_fma(sc[16 * pti[u] + 4 * kq + r] * sj, (double)iacc[u][r], dacc[u][r]);
+          iacc[u] = i32x4{0, 0, 0, 0};
+          if (e >= numel) break;
+        }
+      }
+    }
+  };
+
+  bool have = u0 < u1;
+  int64_t ce0 = 0, cnumel = 0;
+  if (have) {
+    enter_unit();
+    load();
+    put(0);
+    ce0 = le0;
+    cnumel = sg.numel;
+    advance();
+  }
+  __syncthreads();
+  for (int buf = 0; have; buf ^= 1) {
+    const bool more = lu < u1;
+    if (more) load();  // in flight during the MFMAs
+    compute(buf, ce0, cnumel);
+    if (more) {
+      put(buf ^ 1);  // buffer buf ^ 1 was last read before the previous barrier
+      ce0 = le0;
+      cnumel = sg.numel;
+      advance();
+    }
+    __syncthreads();
+    have = more;
+  }
+
+  double* out = partial + (int64_t)blockIdx.x * npairs * 256;
+#pragma unroll
+  for (int u = 0; u < PW; ++u) {
+    const int p = wave + u * kGramWaves;
+    if (p >= npairs) continue;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) out[p * 256 + (4 * kq + r) * 16 + lr] = dacc[u][r];
+  }
+}
+
+// G = the workgroups' slabs added in a fixed order: kRP entries per workgroup here, kBlock / kRP lanes per
+// entry (lane l adds slabs l, l + L, ...; then the L lane sums in lane order).  The entries i <= j of a
+// pair's tile go to both triangles; a diagonal tile's i > j entries and the rows past k are dropped.
+__global__ void __launch_bounds__(kBlock)
+k_gram_q8_reduce(const double* __restrict__ partial, int nslabs, int k, int nt, double* __restrict__ gram) {
+  constexpr int kRP = 8, L = kBlock / kRP;
+  __shared__ double red[L][kRP + 1];
+  const int64_t nent = (int64_t)nt * (nt + 1) / 2 * 256;
+  const int pl = threadIdx.x % kRP, lane = threadIdx.x / kRP;
+  const int64_t p = (int64_t)blockIdx.x * kRP + pl;
+  double s = 0.0;
+  if (p < nent)
+    for (int b = lane; b < nslabs; b += L) s += partial[(int64_t)b * nent + p];
+  red[lane][pl] = s;
+  __syncthreads();
+  if (lane == 0 && p < nent) {
+    double tsum = 0.0;
+    for (int l = 0; l < L; ++l) tsum += red[l][pl];
+    int ti, tj;
+    pair_tiles((int)(p / 256), nt, ti, tj);
+    const int i = 16 * ti + (int)(p % 256) / 16, j = 16 * tj + (int)(p % 16);
+    if (i <= j && j < k) {
+      gram[(int64_t)i * k + j] = tsum;
+      gram[(int64_t)j * k + i] = tsum;
+    }
+  }
+}
+
+// D_ij = max(+0, (G_ii + G_jj) - 2 G_ij), every op rounded once; a NaN passes; D_ii = +0
+__global__ void __launch_bounds__(kBlock)
+k_gram_q8_dist(const double* __restrict__ gram, int k, double* __restrict__ dist) {
+  const int idx = (int)(blockIdx.x * kBlock + threadIdx.x);
+  if (idx >= k * k) return;
+  const int i = idx / k, j = idx % k;
+  double d = 0.0;
+  if (i != j) {
+    const double a = gram[(int64_t)i * k + i] + gram[(int64_t)j * k + j];
+    d = a - 2.0 * gram[idx];
+    d = d != d ? d : d > 0.0 ? d : 0.0;
+  }
+  dist[idx] = d;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t fa_pairwise_gram_q8_scratch_bytes(int32_t num_segments, const int64_t* seg_numel, int32_t k) {
+  if (k < 1 || k > FA_Q8_GRAM_MAX_K || num_segments <= 0 || !seg_numel) return 0;
+  for (int s = 0; s < num_segments; ++s)
+    if (seg_numel[s] < 0) return 0;
+  const int64_t nwg = gram_workgroups(gram_units(num_segments, seg_numel));
+  return sizeof(double) * ((size_t)nwg * gram_plan(k).npairs * 256 + (size_t)k * k);
+}
+
+int fa_pairwise_gram_q8(fa_ctx* ctx, int32_t num_segments, const int64_t* seg_numel, int32_t k, int32_t block,
+                        const void* const* d_q, const void* const* d_scale, void* d_gram, void* d_dist,
+                        void* d_scratch, size_t scratch_bytes, void* hip_stream) {
+  const char* fn = "fa_pairwise_gram_q8";
+  if (!ctx) return fail(FA_ERR_INVALID, "%s: ctx is NULL", fn);
+  const int shift = block_shift(kQ8Gram, block);
+  if (shift < 0) return block_fail(fn, kQ8Gram, block);
+  if (k <= 0 || k > FA_Q8_GRAM_MAX_K || num_segments <= 0)
+    return fail(FA_ERR_INVALID, "%s: k (1 .. %d) and num_segments must be positive", fn, FA_Q8_GRAM_MAX_K);
+  if (!seg_numel || !d_q || !d_scale || !d_dist) return fail(FA_ERR_INVALID, "%s: a table is NULL", fn);
+  int nseg = 0;
+  for (int s = 0; s < num_segments; ++s) {
+    if (seg_numel[s] < 0) return fail(FA_ERR_INVALID, "%s: segment %d has negative numel", fn, s);
+    if (seg_numel[s] == 0) continue;
+    for (int i = 0; i < k; ++i) {
+      const int64_t t = (int64_t)s * k + i;
+      if (!d_q[t]) return fail(FA_ERR_INVALID, "%s: segment %d client %d: q NULL", fn, s, i);
+      if (!d_scale[t] || !al4(d_scale[t]))
+        return fail(FA_ERR_INVALID, "%s: segment %d client %d: scale NULL or not 4-byte aligned", fn, s, i);
+    }
+    ++nseg;
+  }
+  const size_t need = fa_pairwise_gram_q8_scratch_bytes(num_segments, seg_numel, k);
+  if (!d_scratch || ((uintptr_t)d_scratch & 7u) || scratch_bytes < need)
+    return fail(FA_ERR_INVALID, "%s: scratch must hold %zu bytes, 8-byte aligned", fn, need);
+
+  const GramPlan pl = gram_plan(k);
+  const int64_t nunits = gram_units(num_segments, seg_numel);
+  const int nwg = (int)gram_workgroups(nunits);
+  double* slabs = (double*)d_scratch;
+  double* gram = d_gram ? (double*)d_gram : slabs + (size_t)nwg * pl.npairs * 256;
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(FA_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+  hipStream_t st = (hipStream_t)hip_stream;
+  fa_ctx::Slot* slot = nullptr;
+  if (nseg) {
+    const size_t seg_bytes = align16(sizeof(GSeg) * nseg);
+    const size_t ptr_bytes = sizeof(void*) * (size_t)nseg * k;
+    int rc = acquire_slot(ctx, seg_bytes + 2 * ptr_bytes, &slot);
+    if (rc) return rc;
+    char* h = (char*)slot->host;
+    GSeg* hs = (GSeg*)h;
+    const void** hq = (const void**)(h + seg_bytes);
+    const void** hsc = (const void**)(h + seg_bytes + ptr_bytes);
+    int j = 0;
+    int64_t t0 = 0;
+    for (int s = 0; s < num_segments; ++s) {
+      const int64_t n = seg_numel[s];
+      if (n == 0) continue;
+      bool aligned = true;
+      for (int i = 0; i < k; ++i) {
+        hq[(int64_t)j * k + i] = d_q[(int64_t)s * k + i];
+        hsc[(int64_t)j * k + i] = d_scale[(int64_t)s * k + i];
+        aligned = aligned && al16(d_q[(int64_t)s * k + i]);
+      }
+      hs[j] = GSeg{n, t0, j * k, aligned ? 1 : 0};
+      t0 += (n + kUnit - 1) / kUnit;
+      ++j;
+    }
+    rc = stage(slot, seg_bytes + 2 * ptr_bytes, st, true);
+    if (rc) return rc;
+    const char* dv = (const char*)slot->dev;
+    const GSeg* ds = (const GSeg*)dv;
+    const void* const* dq = (const void* const*)(dv + seg_bytes);
+    const void* const* dsc = (const void* const*)(dv + seg_bytes + ptr_bytes);
+    const dim3 grid((unsigned)nwg), blk(kGramThreads);
+#define FA_GRAM(PW) \
+  hipLaunchKernelGGL((k_gram_q8<PW>), grid, blk, 0, st, ds, nseg, dq, dsc, (int)k, pl.nt, pl.W, shift, nunits, slabs)
+    switch (pl.pw) {
+      case 1: FA_GRAM(1); break;
+      case 2: FA_GRAM(2); break;
+      case 3: FA_GRAM(3); break;
+      case 4: FA_GRAM(4); break;
+      default: FA_GRAM(kMaxPW); break;
+    }
+#undef FA_GRAM
+  }
+  // with no slab (all segments empty) the reduction writes +0 everywhere
+  hipLaunchKernelGGL(k_gram_q8_reduce, dim3((unsigned)(pl.npairs * 256 / 8)), dim3(kBlock), 0, st,
+                     (const double*)slabs, nwg, (int)k, pl.nt, gram);
+  hipLaunchKernelGGL(k_gram_q8_dist, dim3((unsigned)((k * k + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                     (const double*)gram, (int)k, (double*)d_dist);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    if (slot) (void)release(slot, st);
+    return fail(FA_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
+  }
+  return slot ? release(slot, st) : FA_OK;
+}
+
+}  // extern "C"

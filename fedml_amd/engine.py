@@ -996,6 +996,74 @@ class AggEngine:
         N.check(rc, "fa_weighted_sum_q8")
         return results
 
+    def pairwise_gram_q8(self, q_segments: Sequence[Sequence[torch.Tensor]],
+                         scale_segments: Sequence[Sequence[torch.Tensor]], block: int = 128,
+                         stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Gram matrix and squared distances of K clients' q8 tensors straight from the quantized bytes
+        (fa_pairwise_gram_q8, include/fedagg_quant_gram.h: exact int32 block products on the int8 matrix
+        cores, scales and sums in float64): q_segments[s][i] / scale_segments[s][i] as ``weighted_sum_q8``
+        takes them.  Returns (G, D), K x K float64 device tensors.  ``block`` is a power of two in
+        [64, 1024].  K > 128 (one launch holds at most 128 clients): clients in blocks of 64, one launch
+        per pair of blocks, its entries kept -- the block order of every sum does not depend on K, so a
+        pair's G and D carry the same bits whichever launch computes them."""
+        what = "pairwise_gram_q8"
+        block = self._check_q8_block(what, block)
+        if block < N.Q8_GRAM_BLOCK_MIN:
+            raise ValueError(f"{what}: block {block} is below {N.Q8_GRAM_BLOCK_MIN}, one int8 matrix instruction; "
+                             "dequantize such tensors (weighted_sum_q8 with one client) and use pairwise_sqdist")
+        if len(q_segments) != len(scale_segments):
+            raise ValueError(f"{what}: q_segments and scale_segments differ in length")
+        k = len(q_segments[0]) if q_segments else 0
+        if k == 0:
+            raise ValueError(f"{what}: no client tensors")
+        numels = []
+        for s, (qseg, sseg) in enumerate(zip(q_segments, scale_segments)):
+            if len(qseg) != k or len(sseg) != k:
+                raise ValueError(f"segment {s}: {len(qseg)} q and {len(sseg)} scale tensors, expected {k}")
+            n = qseg[0].numel()
+            nb = -(-n // block)
+            for i, (q, sc) in enumerate(zip(qseg, sseg)):
+                if q.dtype != torch.int8 or sc.dtype != torch.float32:
+                    raise TypeError(f"segment {s} client {i}: q must be int8 and scale float32 "
+                                    f"(got {q.dtype}, {sc.dtype})")
+                if q.numel() != n or sc.numel() != nb:
+                    raise ValueError(f"segment {s} client {i}: {q.numel()} values and {sc.numel()} scales, "
+                                     f"expected {n} and {nb} in blocks of {block}")
+                _require_device(q, self.device, f"segment {s} client {i} q")
+                _require_device(sc, self.device, f"segment {s} client {i} scale")
+            numels.append(n)
+        nm = N.i64_array(numels)
+
+        def launch(ids):
+            kk = len(ids)
+            g = torch.empty((kk, kk), dtype=torch.float64, device=self.device)
+            d = torch.empty((kk, kk), dtype=torch.float64, device=self.device)
+            with self.lock:
+                need = int(self._lib.fa_pairwise_gram_q8_scratch_bytes(len(numels), nm, kk))
+                scratch = self._scratch("gramq8", need, stream)
+                rc = self._lib.fa_pairwise_gram_q8(
+                    self._ctx, len(numels), nm, kk, block,
+                    N.ptr_array([seg[i].data_ptr() for seg in q_segments for i in ids]),
+                    N.ptr_array([seg[i].data_ptr() for seg in scale_segments for i in ids]),
+                    g.data_ptr(), d.data_ptr(), scratch.data_ptr(), need, self._stream(stream))
+            N.check(rc, "fa_pairwise_gram_q8")
+            return g, d
+
+        if k <= N.Q8_GRAM_MAX_K:
+            return launch(list(range(k)))
+        half = N.Q8_GRAM_MAX_K // 2
+        blocks = [list(range(lo, min(k, lo + half))) for lo in range(0, k, half)]
+        G = torch.zeros((k, k), dtype=torch.float64, device=self.device)
+        D = torch.zeros((k, k), dtype=torch.float64, device=self.device)
+        for a in range(len(blocks)):
+            for b in range(a + 1, len(blocks)):
+                ids = blocks[a] + blocks[b]
+                g, d = launch(ids)
+                idx = torch.tensor(ids, device=self.device)
+                G.index_put_((idx.view(-1, 1), idx.view(1, -1)), g)  # diagonal blocks rewritten, same bits
+                D.index_put_((idx.view(-1, 1), idx.view(1, -1)), d)
+        return G, D
+
     # ------------------------------------------------------------------ 1-bit sign compression (q1)
     @staticmethod
     def _check_q1_block(what: str, block) -> int:

@@ -93,4 +93,8 @@ int fa_weighted_sum_q8(fa_ctx *ctx, int mode, int32_t num_segments, const int64_
 }
 #endif
 
+/* The Gram matrix and pairwise squared distances of k clients' q8 tensors (Krum on the uploaded bytes):
+ * the entries and their contract are specified in their own header, part of this one. */
+#include "fedagg_quant_gram.h"
+
 #endif /* FEDAGG_QUANT_H */
