@@ -11,6 +11,10 @@ import torch
 
 from ....arena import resident_rows
 from ....engine import get_engine
+from ....ml.aggregator.microscaled import MXTensor
+from ....ml.aggregator.quantized import Q8Tensor, _restore
+from ....ml.aggregator.rotated import RotatedTensor
+from ....ml.aggregator.signcompressed import Q1Tensor
 
 _NATIVE = (torch.float32, torch.bfloat16, torch.float16, torch.float64)
 
@@ -59,8 +63,67 @@ def dtype_segments(name: str, grads, keys, eng) -> "OrderedDict":
     return groups
 
 
+def q8_cohort_block(name: str, grads):
+    """The block size when every floating-point key of every client is a `Q8Tensor` of one block size and
+    shape (a block-quantized int8 cohort), None when no client holds a compressed tensor.  Any other
+    compressed format, or plain and Q8 float keys mixed, is a TypeError that names what is supported; a
+    block or shape that differs is a ValueError (as KrumDefense._q8_block).  Messages start with ``name``."""
+    other = next((type(v).__name__ for g in grads for v in g.values()
+                  if isinstance(v, (Q1Tensor, MXTensor, RotatedTensor))), None)
+    if other is not None:
+        raise TypeError(f"{name}: {other} state_dicts are not supported: this defense takes plain tensors or "
+                        "block-quantized int8 (Q8Tensor) floating-point keys")
+    first = grads[0]
+    if not any(isinstance(v, Q8Tensor) for g in grads for v in g.values()):
+        return None
+    fkeys = [k for k, v in first.items() if v.dtype in _NATIVE]
+    for i, g in enumerate(grads):
+        for k in fkeys:
+            if not isinstance(g[k], Q8Tensor):
+                raise TypeError(f"{name}: key {k!r} of client {i} is a plain tensor in a Q8Tensor cohort: plain and "
+                                "Q8Tensor floating-point keys are mixed; supported are all plain tensors or every "
+                                "floating-point key of every client a Q8Tensor")
+        extra = next((k for k, v in g.items() if isinstance(v, Q8Tensor) and k not in set(fkeys)), None)
+        if extra is not None:
+            raise TypeError(f"{name}: key {extra!r} of client {i} is a Q8Tensor where client 0 has none: supported "
+                            "are all plain tensors or every floating-point key of every client a Q8Tensor")
+    block = first[fkeys[0]].block
+    for i, g in enumerate(grads):
+        for k in fkeys:
+            if g[k].block != block:
+                raise ValueError(f"{name}: key {k!r}: client {i} block {g[k].block} != {block} (one block size per call)")
+            if g[k].shape != first[k].shape:
+                raise ValueError(f"{name}: key {k!r}: client {i} shape {g[k].shape} != {first[k].shape}")
+    return block
+
+
+def _defend_q8_keys(name: str, grads, block: int, on_q8: Callable) -> dict:
+    """The Q8Tensor keys of a block-quantized cohort as ONE float32 group: on_q8(eng, qsegs, ssegs, outs,
+    block) runs the defense's passes straight on the quantized tensors -- qsegs[key][client] /
+    ssegs[key][client] flat on the engine's device, outs[key] the views of the group's flat float32 vector to
+    write, each starting on a 16-byte boundary so that whole slots take vector loads and stores.  Returns
+    {key: tensor} in the original shapes and dtypes (one cast, quantized._restore)."""
+    first = grads[0]
+    keys = [k for k, v in first.items() if isinstance(v, Q8Tensor)]
+    dev = next((g[k].q.device for g in grads for k in keys if g[k].q.is_cuda), None)
+    eng = get_engine(dev.index if dev is not None else None)
+    on = lambda t: (t if t.device == eng.device else t.to(eng.device)).contiguous().reshape(-1)  # noqa: E731
+    qsegs = [[on(g[k].q) for g in grads] for k in keys]
+    ssegs = [[on(g[k].scale) for g in grads] for k in keys]
+    starts, pos = [], 0
+    for k in keys:
+        starts.append(pos)
+        pos += -(-first[k].numel() // 4) * 4
+    vec = torch.empty(pos, dtype=torch.float32, device=eng.device)
+    on_q8(eng, qsegs, ssegs, [vec[a:a + first[k].numel()] for k, a in zip(keys, starts)], block)
+    if dev is None:
+        vec = vec.cpu()  # CPU dicts in, CPU tensors out (the copy waits for the launches)
+    return {k: _restore(vec[a:a + first[k].numel()], first[k]) for k, a in zip(keys, starts)}
+
+
 def defend_float_keys(name: str, config, raw_client_grad_list: List[Tuple[float, OrderedDict]],
-                      base_aggregation_func: Callable, on_arena: Callable, on_engine: Callable) -> OrderedDict:
+                      base_aggregation_func: Callable, on_arena: Callable, on_engine: Callable,
+                      on_q8: Callable = None) -> OrderedDict:
     """Every floating-point key of client 0's dict gets the defense's operator over the (>= 1) clients,
     every other key ``base_aggregation_func``'s value; the result is a new OrderedDict in client 0's
     key order on the clients' device (CPU dicts in, CPU tensors out).
@@ -68,17 +131,21 @@ def defend_float_keys(name: str, config, raw_client_grad_list: List[Tuple[float,
     ``on_arena(arena, rows)`` -> {key: tensor}: the updates are rows of ONE arena, float groups only.
     ``on_engine(eng, work)``: otherwise; work = per dtype group (segs, outs), segs[key][client] flat
     tensors on the engine's device and outs[key] the views of the group's flat output to write.
-    Messages start with ``name``."""
+    ``on_q8(eng, qsegs, ssegs, outs, block)``: the defenses that take block-quantized int8 cohorts
+    (`q8_cohort_block`, `_defend_q8_keys`); the result holds plain tensors.  Messages start with ``name``."""
     grads = [g for _, g in raw_client_grad_list]
     first = grads[0]
+    q8_block = q8_cohort_block(name, grads) if on_q8 is not None else None
     fkeys = [k for k, v in first.items() if v.dtype in _NATIVE]
     okeys = [k for k in first if k not in set(fkeys)]
     if okeys and base_aggregation_func is None:
         raise TypeError(f"{name}: keys {okeys} are not floating point and no base aggregation "
                         f"function was given for them")
     result = {}
-    hit = resident_rows(grads) if fkeys and not okeys else None
-    if hit is not None and all(dt in _NATIVE for dt in hit[0].bufs):
+    hit = resident_rows(grads) if fkeys and not okeys and q8_block is None else None
+    if q8_block is not None:
+        result.update(_defend_q8_keys(name, grads, q8_block, on_q8))
+    elif hit is not None and all(dt in _NATIVE for dt in hit[0].bufs):
         result.update(on_arena(*hit))
     elif fkeys:
         dev, eng = engine_of(grads, fkeys)

@@ -21,6 +21,12 @@ otherwise; CPU tensors are moved to the engine's device; its other keys are igno
 a NaN or Inf is dropped and reported by ``get_malicious_client_idxs()``.  The result is a new
 OrderedDict in client 0's key order on the clients' device (CPU dicts in, CPU tensors out); neither
 the inputs nor the center are modified.  ``last_info`` holds the last call's traces.
+
+Block-quantized uploads: when every floating-point key of every client is a `Q8Tensor` of one block size,
+each pass is ONE ``fa_centered_sum_sqdist_q8`` launch over all keys straight from the int8 bytes (no float32
+copy of the clients), in place on one float32 vector into which a "global" center is widened; the result
+holds plain tensors of the original shapes and dtypes.  Mixed plain and Q8Tensor float keys, and the other
+compressed formats, raise TypeError.
 """
 from __future__ import annotations
 
@@ -119,5 +125,22 @@ class CenteredClippingDefense(object):
             self.last_info = cclip_driver(counts, self.iters, self.tau, first,
                                           lambda scales, idx: run(idx, scales, True))
 
+        def on_q8(eng, qsegs, ssegs, outs, block):  # v = outs, float32, in place
+            def run(idx, coef, centered):
+                qs, ss = [[col[i] for i in idx] for col in qsegs], [[col[i] for i in idx] for col in ssegs]
+                return sum_stats([eng.centered_sum_sqdist_q8(qs, ss, outs, coef, block, outs=outs)[1] if centered
+                                  else eng.weighted_sum_sqdist_q8(qs, ss, coef, block, outs=outs)[1]])
+
+            def first(idx):
+                if cen is None:
+                    tot = sum(counts[j] for j in idx)
+                    return run(idx, [counts[j] / tot for j in idx], False)
+                for c, o in zip(cen.values(), outs):  # the float keys in client 0's order, widened to float32
+                    o.copy_(c.reshape(-1))
+                return run(idx, None, True)
+
+            self.last_info = cclip_driver(counts, self.iters, self.tau, first,
+                                          lambda scales, idx: run(idx, scales, True))
+
         return defend_float_keys("centered_clipping", self.config, raw_client_grad_list, base_aggregation_func,
-                                 on_arena, on_engine)
+                                 on_arena, on_engine, on_q8)

@@ -15,6 +15,11 @@ the host).  Non-float keys (a BatchNorm ``num_batches_tracked``) take the base a
 A client whose update holds a NaN or Inf is dropped and reported by ``get_malicious_client_idxs()``.
 The result is a new OrderedDict in client 0's key order on the clients' device (CPU dicts in, CPU
 tensors out); the inputs are not modified.  ``last_info`` holds the last call's traces.
+
+Block-quantized uploads: when every floating-point key of every client is a `Q8Tensor` of one block size,
+each pass is ONE ``fa_weighted_sum_sqdist_q8`` launch over all keys straight from the int8 bytes (no float32
+copy of the clients); the result holds plain tensors of the original shapes and dtypes.  Mixed plain and
+Q8Tensor float keys, and the other compressed formats, raise TypeError.
 """
 from __future__ import annotations
 
@@ -62,5 +67,13 @@ class GeometricMedianDefense(object):
 
             self.last_info = weiszfeld_driver(counts, self.iters, self.nu, step)
 
+        def on_q8(eng, qsegs, ssegs, outs, block):
+            def step(coef, idx):
+                return sum_stats([eng.weighted_sum_sqdist_q8([[col[i] for i in idx] for col in qsegs],
+                                                             [[col[i] for i in idx] for col in ssegs], coef, block,
+                                                             outs=outs)[1]])
+
+            self.last_info = weiszfeld_driver(counts, self.iters, self.nu, step)
+
         return defend_float_keys("geometric_median", self.config, raw_client_grad_list, base_aggregation_func,
-                                 on_arena, on_engine)
+                                 on_arena, on_engine, on_q8)

@@ -38,6 +38,7 @@
 #include "fedagg_robust.h"
 #include "median_common.h"
 #include "median_host.h"
+#include "wsd_common.h"
 
 using namespace fa_detail;
 
@@ -55,44 +56,9 @@ __device__ __forceinline__ void st1(void* p, int64_t e, typename El<DT>::A v) {
 }
 
 constexpr int kS = 4;     // 4-KiB slots per client and workgroup
-constexpr int kKB = 128;  // clients per pass of phase 2 (the LDS block of wave sums)
-constexpr int kRows = kBlock / 16;  // 16-lane DPP rows per workgroup
 enum { kPlain = 0, kCenter = 1, kDist = 2 };  // what a pass forms (wsd_chunk)
 
-// Sum over the lane's 16-lane row, left in every lane of the row: four DPP exchanges (xor 1, xor 2 by
-// quad_perm, then row_half_mirror and row_mirror), plain VALU, in a fixed order.  The rows of a wave
-// are NOT combined here (that would take cross-row permutes through the LDS crossbar, and a wait
-// each): the row leaders store to LDS and the workgroup's 16 row sums are added in row order.
-template <int CTRL>
-__device__ __forceinline__ double dpp_add(double v) {
-  const u32x2 b = __builtin_bit_cast(u32x2, v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)b[0], CTRL, 0xF, 0xF, true);
-  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)b[1], CTRL, 0xF, 0xF, true);
-  return v + __builtin_bit_cast(double, u32x2{lo, hi});
-}
-__device__ __forceinline__ double row_sum(double v) {
-  v = dpp_add<0xB1>(v);   // quad_perm [1, 0, 3, 2]
-  v = dpp_add<0x4E>(v);   // quad_perm [2, 3, 0, 1]
-  v = dpp_add<0x141>(v);  // row_half_mirror
-  v = dpp_add<0x140>(v);  // row_mirror
-  return v;
-}
-
-// the workgroup's row sums of clients [b0, b0 + bn) -> its row of partials, rows added in row order
-__device__ __forceinline__ void flush_rows(double (&red)[kRows][2 * kKB], int b0, int bn, int k,
-                                           double* __restrict__ part) {
-  __syncthreads();
-  for (int t = (int)threadIdx.x; t < 2 * kKB; t += kBlock) {
-    const int i = b0 + (t < kKB ? t : t - kKB);
-    if (i < b0 + bn) {
-      double s = red[0][t];
-#pragma unroll
-      for (int w = 1; w < kRows; ++w) s += red[w][t];
-      part[t < kKB ? i : k + i] = s;
-    }
-  }
-  __syncthreads();
-}
+// row_sum, flush_rows (with kKB and kRows) and k_wsd_reduce are wsd_common.h's, shared with quant_dist.hip.
 
 // One client's kS x V elements of this lane.  VEC: kS 16-byte loads (slot s at byte offset off[s]);
 // else element loads at the clamped element indices off[j] (coalesced across the wave: element j of
@@ -394,37 +360,6 @@ bool wsd_reg_enabled() {  // FA_WSD_REG=0: the generic kernel for every K (A/B);
   return !(e && e[0] == '0');
 }
 
-// stats[e] = the sum over the chunks' rows of partial[row][e] in a fixed order (k_gram_reduce's
-// split, robust.hip): a workgroup of 16 waves takes 16 consecutive entries and splits the rows 64
-// ways (128-byte row reads, each lane its rows in row order), then one lane per entry adds the 64
-// split sums in split order through LDS.
-constexpr int kRW = 16, kRE = 16, kRS = kRW * 64 / kRE;
-__global__ void __launch_bounds__(64 * kRW)
-k_wsd_reduce(const double* __restrict__ partial, int64_t nparts, int n2k, double* __restrict__ stats) {
-  __shared__ double red[kRW * 64];
-  const int el = threadIdx.x % kRE, rs = threadIdx.x / kRE;
-  const int e = blockIdx.x * kRE + el;
-  const bool on = e < n2k;
-  const int ec = on ? e : n2k - 1;
-  double s = 0.0;
-  int64_t b = rs;
-  for (; b + 7 * kRS < nparts; b += 8 * kRS) {  // 8 loads in flight, added in row order
-    double x[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) x[u] = partial[(b + u * kRS) * n2k + ec];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) s += x[u];
-  }
-  for (; b < nparts; b += kRS) s += partial[b * n2k + ec];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  if (threadIdx.x < kRE && on) {
-    double t = 0.0;
-    for (int u = 0; u < kRS; ++u) t += red[u * kRE + threadIdx.x];
-    stats[e] = t;
-  }
-}
-
 int64_t chunk_elems(int dtype) {
   return (int64_t)kS * (FA_TILE_BYTES / (dtype == FA_DTYPE_F64 ? 8 : dtype == FA_DTYPE_F32 ? 4 : 2));
 }
@@ -497,8 +432,7 @@ int wsd_impl(ColArgs a, bool centered, const double* coef, void* d_stats, void* 
           case kCenter: wsd_launch<kCenter>(a.dtype, k, grid, st, ds, n, dp, dcen, dc, part); break;
           default: wsd_launch<kDist>(a.dtype, k, grid, st, ds, n, dp, dcen, dc, part); break;
         }
-        hipLaunchKernelGGL(k_wsd_reduce, dim3((unsigned)((2 * k + kRE - 1) / kRE)), dim3(64 * kRW), 0, st,
-                           (const double*)part, tiles, 2 * k, (double*)d_stats);
+        wsd_reduce_launch(st, part, tiles, k, d_stats);
       });
 }
 

@@ -996,6 +996,96 @@ class AggEngine:
         N.check(rc, "fa_weighted_sum_q8")
         return results
 
+    def _q8_sqdist(self, what: str, q_segments, scale_segments, centers, coef, block, outs, stream, centered: bool):
+        """The two sum-and-squared-distance entries over q8 tensors (include/fedagg_quant_dist.h): the
+        arguments checked as ``weighted_sum_q8`` and ``centered_sum_sqdist`` check theirs, one launch."""
+        block = self._check_q8_block(what, block)
+        if len(q_segments) != len(scale_segments):
+            raise ValueError(f"{what}: q_segments and scale_segments differ in length")
+        k = len(q_segments[0]) if q_segments else 0
+        if k == 0:
+            raise ValueError(f"{what}: no client tensors")
+        dist = centered and coef is None
+        if dist:
+            outs = None
+        elif coef is None or len(coef) != k:
+            raise ValueError(f"{what}: need one coefficient per client")
+        if centered and (centers is None or len(centers) != len(q_segments)):
+            raise ValueError(f"{what}: need one center per segment")
+        numels, q_ptrs, s_ptrs, results = [], [], [], []
+        for s, (qseg, sseg) in enumerate(zip(q_segments, scale_segments)):
+            if len(qseg) != k or len(sseg) != k:
+                raise ValueError(f"segment {s}: {len(qseg)} q and {len(sseg)} scale tensors, expected {k}")
+            n = qseg[0].numel()
+            nb = -(-n // block)
+            for i, (q, sc) in enumerate(zip(qseg, sseg)):
+                if q.dtype != torch.int8 or sc.dtype != torch.float32:
+                    raise TypeError(f"segment {s} client {i}: q must be int8 and scale float32 "
+                                    f"(got {q.dtype}, {sc.dtype})")
+                if q.numel() != n or sc.numel() != nb or not q.is_contiguous() or not sc.is_contiguous():
+                    raise ValueError(f"segment {s} client {i}: {q.numel()} values and {sc.numel()} scales, expected "
+                                     f"{n} and {nb} contiguous ones in blocks of {block}")
+                _require_device(q, self.device, f"segment {s} client {i} q")
+                _require_device(sc, self.device, f"segment {s} client {i} scale")
+                q_ptrs.append(q.data_ptr())
+                s_ptrs.append(sc.data_ptr())
+            if centered:
+                self._check_center(what, centers[s], torch.float32, n, f"segment {s} center")
+            if not dist:
+                if outs is not None:
+                    o = outs[s]
+                    if o.dtype != torch.float32 or o.numel() != n or not o.is_contiguous():
+                        raise ValueError(f"segment {s}: output must be a contiguous float32 tensor of {n} elements")
+                    _require_device(o, self.device, f"segment {s} output")
+                else:
+                    o = torch.empty(qseg[0].shape, dtype=torch.float32, device=self.device)
+                results.append(o)
+            numels.append(n)
+        nm = N.i64_array(numels)
+        stats = torch.empty((2, k), dtype=torch.float64, device=self.device)
+        out_ptrs = None if dist else N.ptr_array([o.data_ptr() for o in results])
+        c = None if dist else N.f64_array(coef)
+        with self.lock:
+            need = int(self._lib.fa_weighted_sum_sqdist_q8_scratch_bytes(len(numels), nm, k))
+            scratch = self._scratch("wsum_sqdist_q8", need, stream)
+            if centered:
+                rc = self._lib.fa_centered_sum_sqdist_q8(
+                    self._ctx, len(numels), nm, k, block, N.ptr_array(q_ptrs), N.ptr_array(s_ptrs),
+                    N.ptr_array([t.data_ptr() for t in centers]), c, out_ptrs, stats.data_ptr(), scratch.data_ptr(),
+                    need, self._stream(stream))
+            else:
+                rc = self._lib.fa_weighted_sum_sqdist_q8(
+                    self._ctx, len(numels), nm, k, block, N.ptr_array(q_ptrs), N.ptr_array(s_ptrs), c, out_ptrs,
+                    stats.data_ptr(), scratch.data_ptr(), need, self._stream(stream))
+        N.check(rc, f"fa_{what}")
+        return (None if dist else results), stats
+
+    def weighted_sum_sqdist_q8(self, q_segments: Sequence[Sequence[torch.Tensor]],
+                               scale_segments: Sequence[Sequence[torch.Tensor]], coef: Sequence[float],
+                               block: int = 128, outs: Optional[Sequence[torch.Tensor]] = None,
+                               stream=None) -> Tuple[List[torch.Tensor], torch.Tensor]:
+        """One smoothed Weiszfeld pass straight from q8 client tensors (fa_weighted_sum_sqdist_q8,
+        include/fedagg_quant_dist.h), one launch and no float32 copy of the clients: the outs are bit for
+        bit ``weighted_sum_q8(q_segments, scale_segments, MUL_W, coef, block)`` and ``stats`` is a [2, K]
+        float64 device tensor: stats[0, i] = sum over all segments of (x_i - out)^2 against the stored out,
+        stats[1, i] = sum of x_i^2, x_i = client i dequantized.  Tensors as ``weighted_sum_q8`` takes them.
+        Returns (outs, stats)."""
+        return self._q8_sqdist("weighted_sum_sqdist_q8", q_segments, scale_segments, None, coef, block, outs, stream,
+                               False)
+
+    def centered_sum_sqdist_q8(self, q_segments: Sequence[Sequence[torch.Tensor]],
+                               scale_segments: Sequence[Sequence[torch.Tensor]], centers: Sequence[torch.Tensor],
+                               coef: Optional[Sequence[float]], block: int = 128,
+                               outs: Optional[Sequence[torch.Tensor]] = None,
+                               stream=None) -> Tuple[Optional[List[torch.Tensor]], torch.Tensor]:
+        """One pass of centered clipping straight from q8 client tensors (fa_centered_sum_sqdist_q8): bit for
+        bit ``centered_sum_sqdist`` over the dequantized float32 tensors, with its stats.  centers[s]: a
+        contiguous float32 tensor of segment s's element count; outs[s] may be centers[s] itself.  ``coef``
+        None: distance-only, nothing but the stats is written and the outs returned are None.  Returns
+        (outs, stats)."""
+        return self._q8_sqdist("centered_sum_sqdist_q8", q_segments, scale_segments, centers, coef, block, outs,
+                               stream, True)
+
     def pairwise_gram_q8(self, q_segments: Sequence[Sequence[torch.Tensor]],
                          scale_segments: Sequence[Sequence[torch.Tensor]], block: int = 128,
                          stream=None) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -96,5 +96,8 @@ int fa_weighted_sum_q8(fa_ctx *ctx, int mode, int32_t num_segments, const int64_
 /* The Gram matrix and pairwise squared distances of k clients' q8 tensors (Krum on the uploaded bytes):
  * the entries and their contract are specified in their own header, part of this one. */
 #include "fedagg_quant_gram.h"
+/* One pass of the geometric median and of centered clipping over k clients' q8 tensors (the weighted sum or
+ * the clipped update, and every client's squared distance to it): likewise. */
+#include "fedagg_quant_dist.h"
 
 #endif /* FEDAGG_QUANT_H */
