@@ -58,6 +58,8 @@ QUANT_SYMBOLS = ("fa_quantize_q8", "fa_weighted_sum_q8")
 Q8_GRAM_SYMBOLS = ("fa_pairwise_gram_q8", "fa_pairwise_gram_q8_scratch_bytes")
 # include/fedagg_quant_dist.h (geometric median and centered clipping on q8 uploads; checked by lib() likewise)
 Q8_DIST_SYMBOLS = ("fa_weighted_sum_sqdist_q8", "fa_centered_sum_sqdist_q8", "fa_weighted_sum_sqdist_q8_scratch_bytes")
+# include/fedagg_quant_col.h (median, trimmed mean and mean around the median on q8 uploads; checked by lib() likewise)
+Q8_COL_SYMBOLS = ("fa_coord_median_q8", "fa_coord_trimmed_mean_q8", "fa_coord_mean_around_median_q8")
 # include/fedagg_dp.h (the differential-privacy entries; checked by lib() like EXPORTED_SYMBOLS)
 DP_SYMBOLS = ("fa_noise_words", "fa_add_noise", "fa_centered_sum_noise", "fa_centered_sum_noise_tiled")
 # include/fedagg_sign.h (the 1-bit sign-compressed entries; checked by lib() like EXPORTED_SYMBOLS)
@@ -73,6 +75,7 @@ Q8_GRAM_MAX_K, Q8_GRAM_BLOCK_MIN = 128, 64  # FA_Q8_GRAM_MAX_K / FA_Q8_GRAM_BLOC
 # FA_Q8_GRAM_UNIT / FA_Q8_GRAM_MIN_UNITS / FA_Q8_GRAM_MAX_WORKGROUPS / FA_Q8_GRAM_STAGE_MIN
 Q8_GRAM_UNIT, Q8_GRAM_MIN_UNITS, Q8_GRAM_MAX_WORKGROUPS, Q8_GRAM_STAGE_MIN = 1024, 4, 512, 256
 Q8_DIST_SLOT = 4096                    # FA_Q8_DIST_SLOT
+Q8_COL_MAX_K, Q8_COL_SLOT = 128, 1024  # FA_Q8_COL_MAX_K / FA_Q8_COL_SLOT
 Q1_BLOCK_MIN, Q1_BLOCK_MAX = 32, 1024  # FA_Q1_BLOCK_MIN / FA_Q1_BLOCK_MAX
 Q1_VOTE_MAX_K = 4095                   # FA_Q1_VOTE_MAX_K
 Q1_SUM_SLOT, Q1_VOTE_SLOT, Q1_GROUP = 8192, 32768, 8  # FA_Q1_SUM_SLOT / FA_Q1_VOTE_SLOT / FA_Q1_GROUP
@@ -333,6 +336,13 @@ def _declare(L):
                                             _P_vp, _P_d, _P_vp, _vp, _vp, ctypes.c_size_t, _vp]
     L.fa_weighted_sum_sqdist_q8_scratch_bytes.restype = ctypes.c_size_t
     L.fa_weighted_sum_sqdist_q8_scratch_bytes.argtypes = [ctypes.c_int32, _P_i64, ctypes.c_int32]
+    _q8_col = [_vp, ctypes.c_int32, _P_i64, ctypes.c_int32, ctypes.c_int32]
+    L.fa_coord_median_q8.restype = ctypes.c_int
+    L.fa_coord_median_q8.argtypes = _q8_col + [_P_vp, _P_vp, _P_vp, _vp]
+    L.fa_coord_trimmed_mean_q8.restype = ctypes.c_int
+    L.fa_coord_trimmed_mean_q8.argtypes = _q8_col + [ctypes.c_int32, _P_vp, _P_vp, _P_vp, _vp]
+    L.fa_coord_mean_around_median_q8.restype = ctypes.c_int
+    L.fa_coord_mean_around_median_q8.argtypes = L.fa_coord_trimmed_mean_q8.argtypes
     L.fa_quantize_q1.restype = ctypes.c_int
     L.fa_quantize_q1.argtypes = L.fa_quantize_q8.argtypes
     L.fa_weighted_sum_q1.restype = ctypes.c_int
@@ -382,7 +392,7 @@ def lib():
             L = ctypes.CDLL(LIB_PATH)
         except OSError as e:
             raise FedAggNativeError(f"cannot load {LIB_PATH}: {e}") from e
-        missing = [s for s in EXPORTED_SYMBOLS + QUANT_SYMBOLS + Q8_GRAM_SYMBOLS + Q8_DIST_SYMBOLS + DP_SYMBOLS + SIGN_SYMBOLS + MX_SYMBOLS
+        missing = [s for s in EXPORTED_SYMBOLS + QUANT_SYMBOLS + Q8_GRAM_SYMBOLS + Q8_DIST_SYMBOLS + Q8_COL_SYMBOLS + DP_SYMBOLS + SIGN_SYMBOLS + MX_SYMBOLS
                    + ROTATE_SYMBOLS if not hasattr(L, s)]
         if missing:
             raise FedAggNativeError(f"{LIB_PATH} lacks symbols {missing}")

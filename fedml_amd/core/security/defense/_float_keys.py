@@ -12,7 +12,7 @@ import torch
 from ....arena import resident_rows
 from ....engine import get_engine
 from ....ml.aggregator.microscaled import MXTensor
-from ....ml.aggregator.quantized import Q8Tensor, _restore
+from ....ml.aggregator.quantized import Q8Tensor, _restore, dequantize_state_dict
 from ....ml.aggregator.rotated import RotatedTensor
 from ....ml.aggregator.signcompressed import Q1Tensor
 
@@ -123,7 +123,7 @@ def _defend_q8_keys(name: str, grads, block: int, on_q8: Callable) -> dict:
 
 def defend_float_keys(name: str, config, raw_client_grad_list: List[Tuple[float, OrderedDict]],
                       base_aggregation_func: Callable, on_arena: Callable, on_engine: Callable,
-                      on_q8: Callable = None) -> OrderedDict:
+                      on_q8: Callable = None, q8_max_k: int = None) -> OrderedDict:
     """Every floating-point key of client 0's dict gets the defense's operator over the (>= 1) clients,
     every other key ``base_aggregation_func``'s value; the result is a new OrderedDict in client 0's
     key order on the clients' device (CPU dicts in, CPU tensors out).
@@ -132,10 +132,16 @@ def defend_float_keys(name: str, config, raw_client_grad_list: List[Tuple[float,
     ``on_engine(eng, work)``: otherwise; work = per dtype group (segs, outs), segs[key][client] flat
     tensors on the engine's device and outs[key] the views of the group's flat output to write.
     ``on_q8(eng, qsegs, ssegs, outs, block)``: the defenses that take block-quantized int8 cohorts
-    (`q8_cohort_block`, `_defend_q8_keys`); the result holds plain tensors.  Messages start with ``name``."""
+    (`q8_cohort_block`, `_defend_q8_keys`); the result holds plain tensors.  ``q8_max_k``: the largest
+    cohort ``on_q8``'s kernels take; a larger block-quantized cohort is dequantized (`dequantize_state_dict`:
+    the sum kernel with one client) and takes the plain route, in each key's original dtype.
+    Messages start with ``name``."""
     grads = [g for _, g in raw_client_grad_list]
-    first = grads[0]
     q8_block = q8_cohort_block(name, grads) if on_q8 is not None else None
+    if q8_block is not None and q8_max_k is not None and len(grads) > q8_max_k:
+        raw_client_grad_list = [(n, dequantize_state_dict(g)) for n, g in raw_client_grad_list]
+        grads, q8_block = [g for _, g in raw_client_grad_list], None
+    first = grads[0]
     fkeys = [k for k, v in first.items() if v.dtype in _NATIVE]
     okeys = [k for k in first if k not in set(fkeys)]
     if okeys and base_aggregation_func is None:

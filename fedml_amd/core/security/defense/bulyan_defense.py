@@ -16,6 +16,12 @@ The contract is the paper's as written in fedagg_robust.h; it is not pinned to a
 Sample counts play no part in the float keys.  Non-float keys (a BatchNorm ``num_batches_tracked``)
 take the base aggregation's value over the chosen clients.  The result is a new OrderedDict in client
 0's key order on the clients' device; the inputs are not modified.
+
+Block-quantized uploads: when every floating-point key of every client is a `Q8Tensor` of one block size,
+stage 1 is Krum's pass on the int8 bytes and stage 2 ONE ``fa_coord_mean_around_median_q8`` launch over the
+chosen clients' bytes, in float32, cast once to a 16-bit key's dtype (more than ``Q8_ROUTE_MAX_K`` chosen
+clients are dequantized first).  Mixed plain and Q8Tensor keys, and the other compressed formats, raise
+TypeError.
 """
 from __future__ import annotations
 
@@ -25,6 +31,12 @@ from typing import Any, Callable, List, Tuple
 from ....bulyan import bulyan_select
 from ._float_keys import defend_float_keys
 from .krum_defense import KrumDefense
+
+
+# The largest count of chosen clients whose block-quantized int8 cohort takes fa_coord_mean_around_median_q8:
+# above it (the kernel's two-lane form) the launch measured no faster than dequantize + the float32 kernel
+# (DESIGN, block-quantized family), so such a cohort is dequantized.
+Q8_ROUTE_MAX_K = 64
 
 
 class BulyanDefense(object):
@@ -56,7 +68,11 @@ class BulyanDefense(object):
         return defend_float_keys(
             "bulyan", self.config, [raw_client_grad_list[i] for i in sorted(sel)], base_aggregation_func,
             lambda arena, rows: arena.mean_around_median(keep, rows),
-            lambda eng, work: [eng.coord_mean_around_median(segs, keep, outs=outs) for segs, outs in work])
+            lambda eng, work: [eng.coord_mean_around_median(segs, keep, outs=outs) for segs, outs in work],
+            # a block-quantized int8 cohort: one launch that reads only the chosen clients' int8 bytes
+            lambda eng, qsegs, ssegs, outs, block: eng.coord_mean_around_median_q8(qsegs, ssegs, keep, block,
+                                                                                   outs=outs),
+            q8_max_k=Q8_ROUTE_MAX_K)
 
     def get_malicious_client_idxs(self):
         return list(self.malicious)

@@ -12,12 +12,18 @@ Every floating-point key of client 0's dict -- BatchNorm running statistics incl
 trimmed mean over the clients, in that key's dtype, one launch per dtype group.  Non-float keys (a
 BatchNorm ``num_batches_tracked``) take the base aggregation's value.  The result is a new
 OrderedDict in client 0's key order on the clients' device; the inputs are not modified.
+
+Block-quantized uploads: when every floating-point key of every client is a `Q8Tensor` of one block size,
+the trimmed mean is ONE ``fa_coord_trimmed_mean_q8`` launch over all keys straight from the int8 bytes, in
+float32, cast once to a 16-bit key's dtype; more than 128 clients are dequantized first.  Mixed plain and
+Q8Tensor float keys, and the other compressed formats, raise TypeError.
 """
 from __future__ import annotations
 
 from collections import OrderedDict
 from typing import Any, Callable, List, Tuple
 
+from ...._native import Q8_COL_MAX_K
 from ._float_keys import defend_float_keys
 
 
@@ -44,4 +50,7 @@ class CoordinateTrimmedMeanDefense(object):
         return defend_float_keys(
             "coordinate_trimmed_mean", self.config, raw_client_grad_list, base_aggregation_func,
             lambda arena, rows: arena.trimmed_mean(b, rows),
-            lambda eng, work: [eng.coord_trimmed_mean(segs, b, outs=outs) for segs, outs in work])
+            lambda eng, work: [eng.coord_trimmed_mean(segs, b, outs=outs) for segs, outs in work],
+            # a block-quantized int8 cohort: one launch over all keys straight from the int8 bytes
+            lambda eng, qsegs, ssegs, outs, block: eng.coord_trimmed_mean_q8(qsegs, ssegs, b, block, outs=outs),
+            q8_max_k=Q8_COL_MAX_K)

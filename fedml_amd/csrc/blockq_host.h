@@ -122,6 +122,57 @@ int block_sum_entry(const char* fn, const BlockFmt& f, int64_t slot, fa_ctx* ctx
       });
 }
 
+// A per-coordinate operator over k <= max_k clients (fedagg_quant_col.h): d_data[s * k + i], d_scale[s * k + i],
+// d_out[s]; a workgroup owns `slot` columns.  Checks in that header's order -- check_arg(), the operator's own
+// argument (the trim, the keep), after the tables and before the segments -- then stages the MSeg and
+// data-pointer tables and, as the payload, the scale pointers and one flag word per segment: kDataAligned here
+// says that the segment's data pointers are all 4-byte aligned (dword loads), kOutAligned that its output is
+// 16-byte aligned.  Calls launch(grid, stream, segs, nseg, data ptrs, scale ptrs, flags, shift).
+template <class ArgCheck, class Launch>
+int block_col_entry(const char* fn, const BlockFmt& f, int64_t slot, int32_t max_k, fa_ctx* ctx, int32_t num_segments,
+                    const int64_t* seg_numel, int32_t k, int32_t block, const void* const* d_data,
+                    const void* const* d_scale, void* const* d_out, void* hip_stream, ArgCheck check_arg,
+                    Launch launch) {
+  if (!ctx) return fail(FA_ERR_INVALID, "%s: ctx is NULL", fn);
+  const int shift = block_shift(f, block);
+  if (shift < 0) return block_fail(fn, f, block);
+  if (k <= 0 || num_segments <= 0) return fail(FA_ERR_INVALID, "%s: k and num_segments must be positive", fn);
+  if (k > max_k)
+    return fail(FA_ERR_INVALID, "%s: k %d exceeds %d: dequantize the clients and use the float entry", fn, k, max_k);
+  if (!seg_numel || !d_data || !d_scale || !d_out) return fail(FA_ERR_INVALID, "%s: a table is NULL", fn);
+  if (const int rc = check_arg()) return rc;
+  int nseg = 0;
+  int64_t tiles = 0;
+  if (const int rc = block_check_segments(fn, f, slot, num_segments, seg_numel, k, d_data, d_scale, d_out, &nseg, &tiles))
+    return rc;
+  if (nseg == 0) return FA_OK;
+
+  const ColArgs a{fn, ctx, FA_DTYPE_F32, num_segments, seg_numel, k, d_data, 0, d_out, hip_stream};
+  const size_t ptr_bytes = sizeof(void*) * (size_t)nseg * k;
+  return col_stage_launch(
+      a, slot, nseg, tiles, ptr_bytes + ((sizeof(int) * (size_t)nseg + 7) & ~size_t(7)),
+      [&](void* h) {
+        const void** hs = (const void**)h;
+        int* hfl = (int*)((char*)h + ptr_bytes);
+        int j = 0;
+        for (int s = 0; s < num_segments; ++s) {
+          if (!seg_numel[s]) continue;
+          bool dal = true;
+          for (int i = 0; i < k; ++i) {
+            hs[(int64_t)j * k + i] = d_scale[(int64_t)s * k + i];
+            dal = dal && al4(d_data[(int64_t)s * k + i]);
+          }
+          hfl[j] = (dal ? kDataAligned : 0) | (al16(d_out[s]) ? kOutAligned : 0);
+          ++j;
+        }
+        if (nseg & 1) hfl[nseg] = 0;  // the padding is staged too
+      },
+      [&](dim3 grid, hipStream_t st, const MSeg* ds, int n, const void* const* dp, const void* payload) {
+        const char* pl = (const char*)payload;
+        launch(grid, st, ds, n, dp, (const void* const*)pl, (const int*)(pl + ptr_bytes), shift);
+      });
+}
+
 // The quantizer of num_segments tensors of one dtype: d_in[s], d_data[s], d_scale[s].  The table holds
 // one "client" per segment (the input), MSeg.out is the segment's data, MSeg.aligned says that input and
 // data are 16-byte aligned, the payload is the scale pointers.  Calls

@@ -67,6 +67,14 @@ __device__ __forceinline__ float fkey_inv(unsigned k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
 }
 
+// The mean around the median (trimmed.hip, quant_col.hip): rank r's share of the walk over ranks
+// lo .. lo + keep - 1 (lo per lane): the value inside the window,
+// -0.0 outside, which a float64 sum that starts at -0.0 passes through unchanged -- so the sum equals
+// the header's, which starts FROM s[lo], bit for bit.
+__device__ __forceinline__ double mam_term(float v, int r, int lo, int keep) {
+  return (double)((unsigned)(r - lo) < (unsigned)keep ? v : -0.0f);
+}
+
 struct MSeg {
   int64_t numel;
   int64_t tile_start;

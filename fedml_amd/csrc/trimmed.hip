@@ -343,12 +343,7 @@ __device__ __forceinline__ void mam_finish(double acc, bool fast, const void* co
   tm_store<DT>(out, e, q);
 }
 
-// rank r's share of the walk over ranks lo .. lo + keep - 1 (lo per lane): the value inside the window,
-// -0.0 outside, which a float64 sum that starts at -0.0 passes through unchanged -- so the sum equals
-// the header's, which starts FROM s[lo], bit for bit.
-__device__ __forceinline__ double mam_term(float v, int r, int lo, int keep) {
-  return (double)((unsigned)(r - lo) < (unsigned)keep ? v : -0.0f);
-}
+// mam_term (rank r's share of the walk over the window): median_common.h, shared with quant_col.hip
 
 // One lane per coordinate, K <= 64: k_tmean_off's loads, sentinels and SortNet<B>; then the median (a
 // uniform select over ranks < B/2), the partners y[r] = s[r + keep] by a uniform barrel shift of the

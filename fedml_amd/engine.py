@@ -996,23 +996,16 @@ class AggEngine:
         N.check(rc, "fa_weighted_sum_q8")
         return results
 
-    def _q8_sqdist(self, what: str, q_segments, scale_segments, centers, coef, block, outs, stream, centered: bool):
-        """The two sum-and-squared-distance entries over q8 tensors (include/fedagg_quant_dist.h): the
-        arguments checked as ``weighted_sum_q8`` and ``centered_sum_sqdist`` check theirs, one launch."""
-        block = self._check_q8_block(what, block)
+    def _q8_clients(self, what: str, q_segments, scale_segments, block: int, contiguous: bool = False):
+        """The q and scale tensors of the q8 entries that read K clients' uploads: one client count, int8 q
+        and float32 scales on the engine's device, every client's element and scale counts (``contiguous``:
+        and contiguous storage).  Returns (K, element counts)."""
         if len(q_segments) != len(scale_segments):
             raise ValueError(f"{what}: q_segments and scale_segments differ in length")
         k = len(q_segments[0]) if q_segments else 0
         if k == 0:
             raise ValueError(f"{what}: no client tensors")
-        dist = centered and coef is None
-        if dist:
-            outs = None
-        elif coef is None or len(coef) != k:
-            raise ValueError(f"{what}: need one coefficient per client")
-        if centered and (centers is None or len(centers) != len(q_segments)):
-            raise ValueError(f"{what}: need one center per segment")
-        numels, q_ptrs, s_ptrs, results = [], [], [], []
+        numels = []
         for s, (qseg, sseg) in enumerate(zip(q_segments, scale_segments)):
             if len(qseg) != k or len(sseg) != k:
                 raise ValueError(f"segment {s}: {len(qseg)} q and {len(sseg)} scale tensors, expected {k}")
@@ -1022,13 +1015,77 @@ class AggEngine:
                 if q.dtype != torch.int8 or sc.dtype != torch.float32:
                     raise TypeError(f"segment {s} client {i}: q must be int8 and scale float32 "
                                     f"(got {q.dtype}, {sc.dtype})")
-                if q.numel() != n or sc.numel() != nb or not q.is_contiguous() or not sc.is_contiguous():
+                if q.numel() != n or sc.numel() != nb or (contiguous and not (q.is_contiguous() and sc.is_contiguous())):
                     raise ValueError(f"segment {s} client {i}: {q.numel()} values and {sc.numel()} scales, expected "
-                                     f"{n} and {nb} contiguous ones in blocks of {block}")
+                                     f"{n} and {nb}{' contiguous ones' if contiguous else ''} in blocks of {block}")
                 _require_device(q, self.device, f"segment {s} client {i} q")
                 _require_device(sc, self.device, f"segment {s} client {i} scale")
-                q_ptrs.append(q.data_ptr())
-                s_ptrs.append(sc.data_ptr())
+            numels.append(n)
+        return k, numels
+
+    def _q8_column_op(self, what: str, q_segments, scale_segments, block, outs, stream, *arg, check=None):
+        """The per-coordinate operators over q8 client tensors (include/fedagg_quant_col.h; ``what`` and the
+        trim or keep as ``_column_op`` takes them): one launch of fa_<what> that reads the uploaded bytes."""
+        block = self._check_q8_block(what, block)
+        k, numels = self._q8_clients(what, q_segments, scale_segments, block, contiguous=True)
+        if k > N.Q8_COL_MAX_K:
+            raise ValueError(f"{what}: {k} clients exceed {N.Q8_COL_MAX_K}; dequantize them (weighted_sum_q8 with one "
+                             f"client) and use {what[:-3]}")
+        arg = [(check or self._check_trim)(b, k, what) for b in arg]
+        results = self._f32_outs(numels, outs)
+        if outs is None:
+            results = [o.view(seg[0].shape) for o, seg in zip(results, q_segments)]
+        elif any(not o.is_contiguous() for o in results):
+            raise ValueError(f"{what}: outputs must be contiguous")
+        rc = getattr(self._lib, "fa_" + what)(
+            self._ctx, len(numels), N.i64_array(numels), k, block, *arg,
+            N.ptr_array([q.data_ptr() for seg in q_segments for q in seg]),
+            N.ptr_array([sc.data_ptr() for seg in scale_segments for sc in seg]),
+            N.ptr_array([o.data_ptr() for o in results]), self._stream(stream))
+        N.check(rc, "fa_" + what)
+        return results
+
+    def coord_median_q8(self, q_segments: Sequence[Sequence[torch.Tensor]],
+                        scale_segments: Sequence[Sequence[torch.Tensor]], block: int = 128,
+                        outs: Optional[Sequence[torch.Tensor]] = None, stream=None) -> List[torch.Tensor]:
+        """Coordinate-wise median straight from K <= 128 clients' q8 tensors (fa_coord_median_q8), one launch
+        and no float32 copy of a client: per coordinate the value of rank (K-1)/2 of x_i = q_i * scale_i
+        (-0.0 below +0.0; a NaN in the column gives NaN).  Tensors as ``weighted_sum_sqdist_q8`` takes them;
+        returns one float32 tensor per key."""
+        return self._q8_column_op("coord_median_q8", q_segments, scale_segments, block, outs, stream)
+
+    def coord_trimmed_mean_q8(self, q_segments: Sequence[Sequence[torch.Tensor]],
+                              scale_segments: Sequence[Sequence[torch.Tensor]], trim: int, block: int = 128,
+                              outs: Optional[Sequence[torch.Tensor]] = None, stream=None) -> List[torch.Tensor]:
+        """Coordinate-wise trimmed mean straight from q8 client tensors (fa_coord_trimmed_mean_q8): bit for
+        bit ``coord_trimmed_mean`` over the dequantized float32 tensors.  Arguments as ``coord_median_q8``."""
+        return self._q8_column_op("coord_trimmed_mean_q8", q_segments, scale_segments, block, outs, stream, trim)
+
+    def coord_mean_around_median_q8(self, q_segments: Sequence[Sequence[torch.Tensor]],
+                                    scale_segments: Sequence[Sequence[torch.Tensor]], keep: int, block: int = 128,
+                                    outs: Optional[Sequence[torch.Tensor]] = None, stream=None) -> List[torch.Tensor]:
+        """Mean around the median (Bulyan's second stage) straight from q8 client tensors
+        (fa_coord_mean_around_median_q8): bit for bit ``coord_mean_around_median`` over the dequantized
+        float32 tensors.  Arguments as ``coord_median_q8``."""
+        return self._q8_column_op("coord_mean_around_median_q8", q_segments, scale_segments, block, outs, stream, keep,
+                                  check=self._check_keep)
+
+    def _q8_sqdist(self, what: str, q_segments, scale_segments, centers, coef, block, outs, stream, centered: bool):
+        """The two sum-and-squared-distance entries over q8 tensors (include/fedagg_quant_dist.h): the
+        arguments checked as ``weighted_sum_q8`` and ``centered_sum_sqdist`` check theirs, one launch."""
+        block = self._check_q8_block(what, block)
+        k, numels = self._q8_clients(what, q_segments, scale_segments, block, contiguous=True)
+        dist = centered and coef is None
+        if dist:
+            outs = None
+        elif coef is None or len(coef) != k:
+            raise ValueError(f"{what}: need one coefficient per client")
+        if centered and (centers is None or len(centers) != len(q_segments)):
+            raise ValueError(f"{what}: need one center per segment")
+        q_ptrs = [q.data_ptr() for seg in q_segments for q in seg]
+        s_ptrs = [sc.data_ptr() for seg in scale_segments for sc in seg]
+        results = []
+        for s, (qseg, n) in enumerate(zip(q_segments, numels)):
             if centered:
                 self._check_center(what, centers[s], torch.float32, n, f"segment {s} center")
             if not dist:
@@ -1040,7 +1097,6 @@ class AggEngine:
                 else:
                     o = torch.empty(qseg[0].shape, dtype=torch.float32, device=self.device)
                 results.append(o)
-            numels.append(n)
         nm = N.i64_array(numels)
         stats = torch.empty((2, k), dtype=torch.float64, device=self.device)
         out_ptrs = None if dist else N.ptr_array([o.data_ptr() for o in results])
@@ -1101,27 +1157,7 @@ class AggEngine:
         if block < N.Q8_GRAM_BLOCK_MIN:
             raise ValueError(f"{what}: block {block} is below {N.Q8_GRAM_BLOCK_MIN}, one int8 matrix instruction; "
                              "dequantize such tensors (weighted_sum_q8 with one client) and use pairwise_sqdist")
-        if len(q_segments) != len(scale_segments):
-            raise ValueError(f"{what}: q_segments and scale_segments differ in length")
-        k = len(q_segments[0]) if q_segments else 0
-        if k == 0:
-            raise ValueError(f"{what}: no client tensors")
-        numels = []
-        for s, (qseg, sseg) in enumerate(zip(q_segments, scale_segments)):
-            if len(qseg) != k or len(sseg) != k:
-                raise ValueError(f"segment {s}: {len(qseg)} q and {len(sseg)} scale tensors, expected {k}")
-            n = qseg[0].numel()
-            nb = -(-n // block)
-            for i, (q, sc) in enumerate(zip(qseg, sseg)):
-                if q.dtype != torch.int8 or sc.dtype != torch.float32:
-                    raise TypeError(f"segment {s} client {i}: q must be int8 and scale float32 "
-                                    f"(got {q.dtype}, {sc.dtype})")
-                if q.numel() != n or sc.numel() != nb:
-                    raise ValueError(f"segment {s} client {i}: {q.numel()} values and {sc.numel()} scales, "
-                                     f"expected {n} and {nb} in blocks of {block}")
-                _require_device(q, self.device, f"segment {s} client {i} q")
-                _require_device(sc, self.device, f"segment {s} client {i} scale")
-            numels.append(n)
+        k, numels = self._q8_clients(what, q_segments, scale_segments, block)
         nm = N.i64_array(numels)
 
         def launch(ids):

@@ -99,5 +99,7 @@ int fa_weighted_sum_q8(fa_ctx *ctx, int mode, int32_t num_segments, const int64_
 /* One pass of the geometric median and of centered clipping over k clients' q8 tensors (the weighted sum or
  * the clipped update, and every client's squared distance to it): likewise. */
 #include "fedagg_quant_dist.h"
+/* The coordinate-wise median, trimmed mean and mean around the median over k clients' q8 tensors: likewise. */
+#include "fedagg_quant_col.h"
 
 #endif /* FEDAGG_QUANT_H */
