@@ -64,6 +64,8 @@ Q8_COL_SYMBOLS = ("fa_coord_median_q8", "fa_coord_trimmed_mean_q8", "fa_coord_me
 DP_SYMBOLS = ("fa_noise_words", "fa_add_noise", "fa_centered_sum_noise", "fa_centered_sum_noise_tiled")
 # include/fedagg_sign.h (the 1-bit sign-compressed entries; checked by lib() like EXPORTED_SYMBOLS)
 SIGN_SYMBOLS = ("fa_quantize_q1", "fa_weighted_sum_q1", "fa_sign_vote_q1")
+# include/fedagg_sign_gram.h (Krum's Gram matrix on q1 uploads; checked by lib() like EXPORTED_SYMBOLS)
+Q1_GRAM_SYMBOLS = ("fa_pairwise_gram_q1", "fa_pairwise_gram_q1_scratch_bytes")
 # include/fedagg_mx.h (the Microscaling entries; checked by lib() like EXPORTED_SYMBOLS)
 MX_SYMBOLS = ("fa_quantize_mx", "fa_weighted_sum_mx")
 # include/fedagg_rotate.h (the randomized Hadamard rotation; checked by lib() like EXPORTED_SYMBOLS)
@@ -79,6 +81,9 @@ Q8_COL_MAX_K, Q8_COL_SLOT = 128, 1024  # FA_Q8_COL_MAX_K / FA_Q8_COL_SLOT
 Q1_BLOCK_MIN, Q1_BLOCK_MAX = 32, 1024  # FA_Q1_BLOCK_MIN / FA_Q1_BLOCK_MAX
 Q1_VOTE_MAX_K = 4095                   # FA_Q1_VOTE_MAX_K
 Q1_SUM_SLOT, Q1_VOTE_SLOT, Q1_GROUP = 8192, 32768, 8  # FA_Q1_SUM_SLOT / FA_Q1_VOTE_SLOT / FA_Q1_GROUP
+Q1_GRAM_MAX_K = 128                    # FA_Q1_GRAM_MAX_K
+# FA_Q1_GRAM_UNIT / FA_Q1_GRAM_MIN_UNITS / FA_Q1_GRAM_MAX_WORKGROUPS / FA_Q1_GRAM_STAGE
+Q1_GRAM_UNIT, Q1_GRAM_MIN_UNITS, Q1_GRAM_MAX_WORKGROUPS, Q1_GRAM_STAGE = 1024, 4, 512, 512
 MX_FP8, MX_FP4 = 0, 1                  # enum fa_mx_format
 MX_BLOCK = 32                          # FA_MX_BLOCK
 MX_FP8_SLOT, MX_FP4_SLOT, MX_GROUP = 4096, 8192, 8  # FA_MX_FP8_SLOT / FA_MX_FP4_SLOT / FA_MX_GROUP
@@ -350,6 +355,10 @@ def _declare(L):
     L.fa_sign_vote_q1.restype = ctypes.c_int
     L.fa_sign_vote_q1.argtypes = [_vp, ctypes.c_int32, _P_i64, ctypes.c_int32, _P_vp, ctypes.c_int32, ctypes.c_double,
                                   _P_vp, _vp]
+    L.fa_pairwise_gram_q1.restype = ctypes.c_int
+    L.fa_pairwise_gram_q1.argtypes = L.fa_pairwise_gram_q8.argtypes
+    L.fa_pairwise_gram_q1_scratch_bytes.restype = ctypes.c_size_t
+    L.fa_pairwise_gram_q1_scratch_bytes.argtypes = [ctypes.c_int32, _P_i64, ctypes.c_int32]
     L.fa_quantize_mx.restype = ctypes.c_int
     L.fa_quantize_mx.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int32, _P_i64, _P_vp, _P_vp, _P_vp, _vp]
     L.fa_weighted_sum_mx.restype = ctypes.c_int
@@ -392,7 +401,7 @@ def lib():
             L = ctypes.CDLL(LIB_PATH)
         except OSError as e:
             raise FedAggNativeError(f"cannot load {LIB_PATH}: {e}") from e
-        missing = [s for s in EXPORTED_SYMBOLS + QUANT_SYMBOLS + Q8_GRAM_SYMBOLS + Q8_DIST_SYMBOLS + Q8_COL_SYMBOLS + DP_SYMBOLS + SIGN_SYMBOLS + MX_SYMBOLS
+        missing = [s for s in EXPORTED_SYMBOLS + QUANT_SYMBOLS + Q8_GRAM_SYMBOLS + Q8_DIST_SYMBOLS + Q8_COL_SYMBOLS + DP_SYMBOLS + SIGN_SYMBOLS + Q1_GRAM_SYMBOLS + MX_SYMBOLS
                    + ROTATE_SYMBOLS if not hasattr(L, s)]
         if missing:
             raise FedAggNativeError(f"{LIB_PATH} lacks symbols {missing}")

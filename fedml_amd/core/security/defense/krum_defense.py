@@ -18,6 +18,10 @@ least 64, the distances come from ``fa_pairwise_gram_q8`` -- the Gram matrix str
 bytes on the int8 matrix cores, no float32 copy of the clients -- and the selected clients' Q8 dicts
 are returned untouched for `aggregate_q8`.  Blocks of 16 or 32 (below one int8 matrix instruction) are
 dequantized key by key (``weighted_sum_q8`` with one client) and take the float32 path.
+
+1-bit sign uploads: a cohort whose weight keys are all `Q1Tensor` of one block size (any the format has)
+gets its distances from ``fa_pairwise_gram_q1`` -- XOR and population counts on the uploaded words -- and
+the selected clients' Q1 dicts are returned untouched for `aggregate_q1`.
 """
 from __future__ import annotations
 
@@ -73,18 +77,22 @@ class KrumDefense(object):
         as vectorize_weight does), one device pass; for bf16 / f16 models every difference is
         rounded to that dtype as the reference's ``v_i - v_j`` does."""
         keys = [k for k in grads[0].keys() if is_weight_param(k)]
-        q8_block = self._q8_block(grads, keys)
-        if q8_block is not None:
-            dev = next((g[k].q.device for g in grads for k in keys if g[k].q.is_cuda), None)
+        fmt = self._block_format(grads, keys)
+        if fmt is not None:
+            cls, block = fmt
+            data = "q" if cls is Q8Tensor else "bits"
+            dev = next((getattr(g[k], data).device for g in grads for k in keys if getattr(g[k], data).is_cuda), None)
             eng = get_engine(dev.index if dev is not None else None)
             on = lambda t: t if t.device == eng.device else t.to(eng.device)  # noqa: E731
-            if q8_block >= Q8_GRAM_BLOCK_MIN:
-                _, D = eng.pairwise_gram_q8([[on(g[k].q).reshape(-1) for g in grads] for k in keys],
-                                            [[on(g[k].scale) for g in grads] for k in keys], q8_block)
-                return D.cpu().numpy()
+            dseg = [[on(getattr(g[k], data)).reshape(-1) for g in grads] for k in keys]
+            sseg = [[on(g[k].scale) for g in grads] for k in keys]
+            if cls is Q1Tensor:
+                return eng.pairwise_gram_q1(dseg, sseg, [grads[0][k].numel() for k in keys], block)[1].cpu().numpy()
+            if block >= Q8_GRAM_BLOCK_MIN:
+                return eng.pairwise_gram_q8(dseg, sseg, block)[1].cpu().numpy()
             # blocks of 16 or 32: the weight keys dequantized (one launch per client), then the float path
             grads = [dict(zip(keys, eng.weighted_sum_q8([[on(g[k].q)] for k in keys], [[on(g[k].scale)] for k in keys],
-                                                        SUM, None, q8_block))) for g in grads]
+                                                        SUM, None, block))) for g in grads]
         vdt = self.vector_dtype(grads)
         diff_dt = vdt if vdt in (torch.bfloat16, torch.float16, torch.float64) else torch.float32
         in_dt = torch.float64 if diff_dt == torch.float64 else torch.float32
@@ -102,25 +110,30 @@ class KrumDefense(object):
         return eng.pairwise_sqdist(segs, diff_dtype=diff_dt).cpu().numpy()
 
     @staticmethod
-    def _q8_block(grads, keys):
-        """The block size when every weight key of every client is a Q8Tensor, None when none is one;
-        anything else is an error."""
+    def _block_format(grads, keys):
+        """(Q8Tensor or Q1Tensor, the block size) when every weight key of every client is of that one class,
+        None when none is of either; anything else is an error."""
         other = next((type(g[k]).__name__ for g in grads for k in keys
-                      if isinstance(g[k], (Q1Tensor, MXTensor, RotatedTensor))), None)
+                      if isinstance(g[k], (MXTensor, RotatedTensor))), None)
         if other is not None:
-            raise TypeError(f"KrumDefense: {other} state_dicts are not supported: Krum takes plain tensors or "
-                            "block-quantized int8 (Q8Tensor) weight keys")
+            raise TypeError(f"KrumDefense: {other} state_dicts are not supported: Krum takes plain tensors, "
+                            "block-quantized int8 (Q8Tensor) or 1-bit sign (Q1Tensor) weight keys")
         first = grads[0]
-        qset = {k for k in keys if isinstance(first[k], Q8Tensor)}
+        cls = next((type(g[k]) for g in grads for k in keys if isinstance(g[k], (Q8Tensor, Q1Tensor))), None)
+        if cls is None:
+            return None
+        name = cls.__name__
+        qset = {k for k in keys if isinstance(first[k], cls)}
         for i, g in enumerate(grads):
             for k in keys:
-                if isinstance(g[k], Q8Tensor) != (k in qset):
-                    raise TypeError(f"key {k!r}: client {i} {'has' if isinstance(g[k], Q8Tensor) else 'lacks'} a "
-                                    f"Q8Tensor where client 0 {'has' if k in qset else 'lacks'} one")
+                if isinstance(g[k], cls) != (k in qset):
+                    raise TypeError(f"key {k!r}: client {i} {'has' if isinstance(g[k], cls) else 'lacks'} a "
+                                    f"{name} where client 0 {'has' if k in qset else 'lacks'} one")
         if not qset:
             return None
         if len(qset) != len(keys):
-            raise TypeError("KrumDefense: plain and Q8Tensor weight keys are mixed: quantize every weight key or none")
+            raise TypeError(f"KrumDefense: {name} and other weight keys are mixed: compress every weight key the "
+                            "same way or none")
         block = first[keys[0]].block
         for i, g in enumerate(grads):
             for k in keys:
@@ -128,7 +141,7 @@ class KrumDefense(object):
                     raise ValueError(f"key {k!r}: client {i} block {g[k].block} != {block} (one block size per call)")
                 if g[k].shape != first[k].shape:
                     raise ValueError(f"key {k!r}: client {i} shape {g[k].shape} != {first[k].shape}")
-        return block
+        return cls, block
 
     def _compute_krum_score(self, grads):
         D = self.pairwise_sq_distances(grads)

@@ -17,8 +17,9 @@
 // pairs per wave, is the template parameter, so every accumulator has a fixed register).  Per pair the
 // wave keeps 4 int32 and 4 float64 accumulators per lane; a block of B elements is B / 64 MFMAs into
 // the int32 ones (across stages when B > W), then one scale step: acc64 = fma(s_i s_j, (double)I, acc64).
-// Per-workgroup float64 slabs ([pair][16][16]) go to the scratch; k_gram_q8_reduce adds them in a fixed
-// order and writes both triangles of G; k_gram_q8_dist forms D from G's bits.
+// Per-workgroup float64 slabs ([pair][16][16]) go to the scratch; k_gram_reduce adds them in a fixed
+// order and writes both triangles of G; k_gram_dist forms D from G's bits (gram_common.h, shared with the
+// q1 Gram kernel of signgram.hip, as are the work split and the staged tables).
 // Numbers and the resource use: DESIGN.md (block-quantized family).
 #include <hip/hip_runtime.h>
 
@@ -28,6 +29,7 @@
 #include "fa_internal.h"
 #include "fedagg_quant.h"
 #include "blockq_host.h"
+#include "gram_common.h"
 #include "median_common.h"
 
 using namespace fa_detail;
@@ -47,14 +49,6 @@ static_assert(2 * kGramLds <= 160 * 1024, "two workgroups per CU");
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
-struct GSeg {
-  int64_t numel;
-  int64_t tile_start;  // first unit of this segment (find_seg keys on it)
-  int32_t ptr_base;
-  int32_t aligned;     // every q pointer of the segment is 16-byte aligned
-};
-static_assert(sizeof(GSeg) == 24, "GSeg layout");
-
 constexpr BlockFmt kQ8Gram{"q", FA_Q8_GRAM_BLOCK_MIN, FA_Q8_BLOCK_MAX, 0};
 
 struct GramPlan { int nt, npairs, pw, W; };
@@ -65,24 +59,6 @@ GramPlan gram_plan(int k) {
   p.pw = (p.npairs + kGramWaves - 1) / kGramWaves;
   p.W = p.nt <= 2 ? 1024 : p.nt <= 4 ? 512 : FA_Q8_GRAM_STAGE_MIN;
   return p;
-}
-
-int64_t gram_units(int32_t num_segments, const int64_t* seg_numel) {
-  int64_t n = 0;
-  for (int s = 0; s < num_segments; ++s)
-    if (seg_numel[s] > 0) n += (seg_numel[s] + kUnit - 1) / kUnit;
-  return n;
-}
-int64_t gram_workgroups(int64_t units) {
-  return std::min<int64_t>(FA_Q8_GRAM_MAX_WORKGROUPS, (units + FA_Q8_GRAM_MIN_UNITS - 1) / FA_Q8_GRAM_MIN_UNITS);
-}
-
-// pair -> (ti, tj), ti <= tj: row-major over the upper triangle of nt tiles
-__device__ __forceinline__ void pair_tiles(int p, int nt, int& ti, int& tj) {
-  int r = 0, rem = p;
-  while (rem >= nt - r) { rem -= nt - r; ++r; }
-  ti = r;
-  tj = r + rem;
 }
 
 template <int PW>
@@ -250,49 +226,6 @@ k_gram_q8(const GSeg* __restrict__ segs, int nseg, const void* const* __restrict
   }
 }
 
-// G = the workgroups' slabs added in a fixed order: kRP entries per workgroup here, kBlock / kRP lanes per
-// entry (lane l adds slabs l, l + L, ...; then the L lane sums in lane order).  The entries i <= j of a
-// pair's tile go to both triangles; a diagonal tile's i > j entries and the rows past k are dropped.
-__global__ void __launch_bounds__(kBlock)
-k_gram_q8_reduce(const double* __restrict__ partial, int nslabs, int k, int nt, double* __restrict__ gram) {
-  constexpr int kRP = 8, L = kBlock / kRP;
-  __shared__ double red[L][kRP + 1];
-  const int64_t nent = (int64_t)nt * (nt + 1) / 2 * 256;
-  const int pl = threadIdx.x % kRP, lane = threadIdx.x / kRP;
-  const int64_t p = (int64_t)blockIdx.x * kRP + pl;
-  double s = 0.0;
-  if (p < nent)
-    for (int b = lane; b < nslabs; b += L) s += partial[(int64_t)b * nent + p];
-  red[lane][pl] = s;
-  __syncthreads();
-  if (lane == 0 && p < nent) {
-    double tsum = 0.0;
-    for (int l = 0; l < L; ++l) tsum += red[l][pl];
-    int ti, tj;
-    pair_tiles((int)(p / 256), nt, ti, tj);
-    const int i = 16 * ti + (int)(p % 256) / 16, j = 16 * tj + (int)(p % 16);
-    if (i <= j && j < k) {
-      gram[(int64_t)i * k + j] = tsum;
-      gram[(int64_t)j * k + i] = tsum;
-    }
-  }
-}
-
-// D_ij = max(+0, (G_ii + G_jj) - 2 G_ij), every op rounded once; a NaN passes; D_ii = +0
-__global__ void __launch_bounds__(kBlock)
-k_gram_q8_dist(const double* __restrict__ gram, int k, double* __restrict__ dist) {
-  const int idx = (int)(blockIdx.x * kBlock + threadIdx.x);
-  if (idx >= k * k) return;
-  const int i = idx / k, j = idx % k;
-  double d = 0.0;
-  if (i != j) {
-    const double a = gram[(int64_t)i * k + i] + gram[(int64_t)j * k + j];
-    d = a - 2.0 * gram[idx];
-    d = d != d ? d : d > 0.0 ? d : 0.0;
-  }
-  dist[idx] = d;
-}
-
 }  // namespace
 
 extern "C" {
@@ -301,7 +234,8 @@ size_t fa_pairwise_gram_q8_scratch_bytes(int32_t num_segments, const int64_t* se
   if (k < 1 || k > FA_Q8_GRAM_MAX_K || num_segments <= 0 || !seg_numel) return 0;
   for (int s = 0; s < num_segments; ++s)
     if (seg_numel[s] < 0) return 0;
-  const int64_t nwg = gram_workgroups(gram_units(num_segments, seg_numel));
+  const int64_t nwg = gram_workgroups(gram_units(num_segments, seg_numel, kUnit), FA_Q8_GRAM_MIN_UNITS,
+                                      FA_Q8_GRAM_MAX_WORKGROUPS);
   return sizeof(double) * ((size_t)nwg * gram_plan(k).npairs * 256 + (size_t)k * k);
 }
 
@@ -332,47 +266,21 @@ int fa_pairwise_gram_q8(fa_ctx* ctx, int32_t num_segments, const int64_t* seg_nu
     return fail(FA_ERR_INVALID, "%s: scratch must hold %zu bytes, 8-byte aligned", fn, need);
 
   const GramPlan pl = gram_plan(k);
-  const int64_t nunits = gram_units(num_segments, seg_numel);
-  const int nwg = (int)gram_workgroups(nunits);
+  const int64_t nunits = gram_units(num_segments, seg_numel, kUnit);
+  const int nwg = (int)gram_workgroups(nunits, FA_Q8_GRAM_MIN_UNITS, FA_Q8_GRAM_MAX_WORKGROUPS);
   double* slabs = (double*)d_scratch;
   double* gram = d_gram ? (double*)d_gram : slabs + (size_t)nwg * pl.npairs * 256;
   DeviceGuard g(ctx->device);
   if (!g.ok) return fail(FA_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
   hipStream_t st = (hipStream_t)hip_stream;
-  fa_ctx::Slot* slot = nullptr;
+  GramTables tb;
   if (nseg) {
-    const size_t seg_bytes = align16(sizeof(GSeg) * nseg);
-    const size_t ptr_bytes = sizeof(void*) * (size_t)nseg * k;
-    int rc = acquire_slot(ctx, seg_bytes + 2 * ptr_bytes, &slot);
+    const int rc = gram_stage_tables(ctx, num_segments, seg_numel, k, nseg, kUnit, d_q, d_scale, st, &tb);
     if (rc) return rc;
-    char* h = (char*)slot->host;
-    GSeg* hs = (GSeg*)h;
-    const void** hq = (const void**)(h + seg_bytes);
-    const void** hsc = (const void**)(h + seg_bytes + ptr_bytes);
-    int j = 0;
-    int64_t t0 = 0;
-    for (int s = 0; s < num_segments; ++s) {
-      const int64_t n = seg_numel[s];
-      if (n == 0) continue;
-      bool aligned = true;
-      for (int i = 0; i < k; ++i) {
-        hq[(int64_t)j * k + i] = d_q[(int64_t)s * k + i];
-        hsc[(int64_t)j * k + i] = d_scale[(int64_t)s * k + i];
-        aligned = aligned && al16(d_q[(int64_t)s * k + i]);
-      }
-      hs[j] = GSeg{n, t0, j * k, aligned ? 1 : 0};
-      t0 += (n + kUnit - 1) / kUnit;
-      ++j;
-    }
-    rc = stage(slot, seg_bytes + 2 * ptr_bytes, st, true);
-    if (rc) return rc;
-    const char* dv = (const char*)slot->dev;
-    const GSeg* ds = (const GSeg*)dv;
-    const void* const* dq = (const void* const*)(dv + seg_bytes);
-    const void* const* dsc = (const void* const*)(dv + seg_bytes + ptr_bytes);
     const dim3 grid((unsigned)nwg), blk(kGramThreads);
 #define FA_GRAM(PW) \
-  hipLaunchKernelGGL((k_gram_q8<PW>), grid, blk, 0, st, ds, nseg, dq, dsc, (int)k, pl.nt, pl.W, shift, nunits, slabs)
+  hipLaunchKernelGGL((k_gram_q8<PW>), grid, blk, 0, st, tb.segs, nseg, tb.data, tb.scale, (int)k, pl.nt, pl.W, shift, nunits, \
+                     slabs)
     switch (pl.pw) {
       case 1: FA_GRAM(1); break;
       case 2: FA_GRAM(2); break;
@@ -382,17 +290,13 @@ int fa_pairwise_gram_q8(fa_ctx* ctx, int32_t num_segments, const int64_t* seg_nu
     }
 #undef FA_GRAM
   }
-  // with no slab (all segments empty) the reduction writes +0 everywhere
-  hipLaunchKernelGGL(k_gram_q8_reduce, dim3((unsigned)(pl.npairs * 256 / 8)), dim3(kBlock), 0, st,
-                     (const double*)slabs, nwg, (int)k, pl.nt, gram);
-  hipLaunchKernelGGL(k_gram_q8_dist, dim3((unsigned)((k * k + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                     (const double*)gram, (int)k, (double*)d_dist);
+  gram_reduce_dist(st, slabs, nwg, (int)k, pl.nt, gram, (double*)d_dist);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
-    if (slot) (void)release(slot, st);
+    if (tb.slot) (void)release(tb.slot, st);
     return fail(FA_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
   }
-  return slot ? release(slot, st) : FA_OK;
+  return tb.slot ? release(tb.slot, st) : FA_OK;
 }
 
 }  // extern "C"

@@ -1175,9 +1175,14 @@ class AggEngine:
             N.check(rc, "fa_pairwise_gram_q8")
             return g, d
 
-        if k <= N.Q8_GRAM_MAX_K:
+        return self._gram_blocks(k, N.Q8_GRAM_MAX_K, launch)
+
+    def _gram_blocks(self, k: int, max_k: int, launch) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(G, D) of k clients from ``launch(ids) -> (g, d)``, which holds at most ``max_k`` clients: one launch,
+        or clients in blocks of max_k / 2 and one launch per pair of blocks, its entries kept."""
+        if k <= max_k:
             return launch(list(range(k)))
-        half = N.Q8_GRAM_MAX_K // 2
+        half = max_k // 2
         blocks = [list(range(lo, min(k, lo + half))) for lo in range(0, k, half)]
         G = torch.zeros((k, k), dtype=torch.float64, device=self.device)
         D = torch.zeros((k, k), dtype=torch.float64, device=self.device)
@@ -1260,6 +1265,24 @@ class AggEngine:
                 ptrs.append(b.data_ptr())
         return k, ptrs
 
+    def _q1_scale_table(self, scale_segments, numels, k: int, block: int) -> List[int]:
+        """Validates scale_segments[s][i] (float32, ceil(numels[s] / block) scales, on the device); returns the
+        pointer table [s * k + i]."""
+        s_ptrs = []
+        for s, (sseg, n) in enumerate(zip(scale_segments, numels)):
+            nb = -(-int(n) // block)
+            if len(sseg) != k:
+                raise ValueError(f"segment {s}: {len(sseg)} scale tensors, expected {k}")
+            for i, sc in enumerate(sseg):
+                if sc.dtype != torch.float32:
+                    raise TypeError(f"segment {s} client {i}: scale must be float32 (got {sc.dtype})")
+                if sc.numel() != nb:
+                    raise ValueError(f"segment {s} client {i}: {sc.numel()} scales, expected {nb} "
+                                     f"for {n} elements in blocks of {block}")
+                _require_device(sc, self.device, f"segment {s} client {i} scale")
+                s_ptrs.append(sc.data_ptr())
+        return s_ptrs
+
     def _f32_outs(self, numels, outs) -> List[torch.Tensor]:
         if outs is None:
             return [torch.empty(int(n), dtype=torch.float32, device=self.device) for n in numels]
@@ -1289,19 +1312,7 @@ class AggEngine:
         k, b_ptrs = self._q1_bits_table("weighted_sum_q1", bits_segments, numels)
         if mode != SUM and (coef is None or len(coef) != k):
             raise ValueError("weighted_sum_q1: need one coefficient per client")
-        s_ptrs = []
-        for s, (sseg, n) in enumerate(zip(scale_segments, numels)):
-            nb = -(-int(n) // block)
-            if len(sseg) != k:
-                raise ValueError(f"segment {s}: {len(sseg)} scale tensors, expected {k}")
-            for i, sc in enumerate(sseg):
-                if sc.dtype != torch.float32:
-                    raise TypeError(f"segment {s} client {i}: scale must be float32 (got {sc.dtype})")
-                if sc.numel() != nb:
-                    raise ValueError(f"segment {s} client {i}: {sc.numel()} scales, expected {nb} "
-                                     f"for {n} elements in blocks of {block}")
-                _require_device(sc, self.device, f"segment {s} client {i} scale")
-                s_ptrs.append(sc.data_ptr())
+        s_ptrs = self._q1_scale_table(scale_segments, numels, k, block)
         results = self._f32_outs(numels, outs)
         rc = self._lib.fa_weighted_sum_q1(
             self._ctx, int(mode), len(numels), N.i64_array(numels), k, block, N.ptr_array(b_ptrs),
@@ -1309,6 +1320,40 @@ class AggEngine:
             N.ptr_array([o.data_ptr() for o in results]), self._stream(stream))
         N.check(rc, "fa_weighted_sum_q1")
         return results
+
+    def pairwise_gram_q1(self, bits_segments: Sequence[Sequence[torch.Tensor]],
+                         scale_segments: Sequence[Sequence[torch.Tensor]], numels: Sequence[int], block: int = 128,
+                         stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Gram matrix and squared distances of K clients' q1 tensors straight from the uploaded bits
+        (fa_pairwise_gram_q1, include/fedagg_sign_gram.h: a block's product is n - 2 popcount(w_i ^ w_j),
+        scales and sums in float64): bits_segments[s][i] / scale_segments[s][i] / numels[s] as
+        ``weighted_sum_q1`` takes them.  Returns (G, D), K x K float64 device tensors.  K > 128 is split as
+        ``pairwise_gram_q8`` splits it, with the same bits."""
+        what = "pairwise_gram_q1"
+        block = self._check_q1_block(what, block)
+        if len(bits_segments) != len(scale_segments):
+            raise ValueError(f"{what}: bits_segments and scale_segments differ in length")
+        if len(bits_segments) == 0:
+            raise ValueError(f"{what}: no segments")
+        k, b_ptrs = self._q1_bits_table(what, bits_segments, numels)
+        s_ptrs = self._q1_scale_table(scale_segments, numels, k, block)
+        nm, nseg = N.i64_array(numels), len(numels)
+
+        def launch(ids):
+            kk = len(ids)
+            g = torch.empty((kk, kk), dtype=torch.float64, device=self.device)
+            d = torch.empty((kk, kk), dtype=torch.float64, device=self.device)
+            with self.lock:
+                need = int(self._lib.fa_pairwise_gram_q1_scratch_bytes(nseg, nm, kk))
+                scratch = self._scratch("gramq1", need, stream)
+                rc = self._lib.fa_pairwise_gram_q1(
+                    self._ctx, nseg, nm, kk, block, N.ptr_array([b_ptrs[s * k + i] for s in range(nseg) for i in ids]),
+                    N.ptr_array([s_ptrs[s * k + i] for s in range(nseg) for i in ids]),
+                    g.data_ptr(), d.data_ptr(), scratch.data_ptr(), need, self._stream(stream))
+            N.check(rc, "fa_pairwise_gram_q1")
+            return g, d
+
+        return self._gram_blocks(k, N.Q1_GRAM_MAX_K, launch)
 
     def sign_vote_q1(self, bits_segments: Sequence[Sequence[torch.Tensor]], numels: Sequence[int],
                      threshold: int = 1, step: float = 1.0, outs: Optional[Sequence[torch.Tensor]] = None,

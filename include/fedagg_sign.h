@@ -28,7 +28,8 @@
  *
  * Out of scope: error feedback and stochastic signs (the client's business: it applies either before
  * this format), tile-interleaved arena storage, a collective (RCCL) path, the robust defenses on q1
- * inputs, and per-client vote weights (every client has one vote).
+ * inputs other than Krum (its Gram matrix straight from the bits is fedagg_sign_gram.h's), and per-client
+ * vote weights (every client has one vote).
  */
 #ifndef FEDAGG_SIGN_H
 #define FEDAGG_SIGN_H
